@@ -1,7 +1,13 @@
 #!/usr/bin/env python
 """Benchmark of the match/rank hot path (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run builds the index, warms up, times the K steps and prints the result line (value, ms_per_step, the host
+sections of the timed batches, the index); --dump-outputs DIR also writes the rows the last timed step delivered
+(dump_outputs).  Everything else below — roofline, kernel durations, latency and server legs, the C3 / C5 sub-legs,
+parity against the oracle, cpu_baseline, hook parity — runs only with --full, within --full-seconds of wall time: the
+reference legs (their index build depends on the host's cores) take what is left of it, or are given up with the reason.
 
 N > 1 needs one process per GPU: when started as a plain `python bench.py --gpus N` the script re-executes
 itself under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1` (the form
@@ -50,6 +56,8 @@ SECTOR = 64                # bytes one random gather costs at the memory side (t
 CORPUS_SEED = 0x5EED0001
 QUERY_SEED = 0x5EED0002
 BATCH = int(os.environ.get("XGM_BENCH_BATCH", "256"))          # (diagnostics only: the metric is quoted on batches of 256)
+T_START = time.time()
+REF_RESERVE_S = 240        # what the reference leg needs after its index build (time-boxed timings, parity query run), --full-seconds
 
 
 def parse_args():
@@ -58,6 +66,12 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batches-per-step", type=int, default=16, help="batches of 256 queries one step submits")
+    ap.add_argument("--full", action="store_true", help="also run every leg beyond the headline timed region (roofline, latency, server, C3 / C5 sub-legs, "
+                    "parity, cpu_baseline, hook parity); the --no-* switches below select among them")
+    ap.add_argument("--full-seconds", type=float, default=540.0, help="wall-clock allowance of a --full run (0 = none): the reference legs, whose index build "
+                    "depends on the host's cores, fit into what is left of it or are given up with the reason (the port is reported); at 10 M documents they "
+                    "take ~13 min on a 256-thread host")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the rows the last timed step delivered to the host as DIR/<name>.npy (float64)")
     ap.add_argument("--in-flight", type=int, default=2, help="batches in flight (xgm_get_mset_batch_begin ... xgm_batch_end); measured on the MI355X, round 5: 2 beats 3 by 4-7 %% on C2 (the host needs 0.15 ms per batch, the kernel 0.35: one batch queued behind the running one is enough, a third only adds queue traffic)")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the C3 / C5 sub-legs of the default (C2) line")
     ap.add_argument("--no-hook-parity", action="store_true", help="skip the hook-on == hook-off leg on the reference's own glass index")
@@ -83,6 +97,22 @@ def parse_args():
     ap.add_argument("--no-latency", action="store_true", help="skip the one-query-in-flight leg (profiling runs)")
     ap.add_argument("--threads", type=int, default=64, help="server leg: T host threads, each with one xgm_get_mset_batch(nq=1) in flight (0: skip)")
     return ap.parse_args()
+
+
+def seconds_left(args):
+    """Seconds of --full-seconds still unspent (None: no allowance)."""
+    return None if not args.full_seconds else args.full_seconds - (time.time() - T_START)
+
+
+def ref_budget(args):
+    """Time the reference's index build may take: --ref-build-budget, within what --full-seconds leaves after REF_RESERVE_S (None: no limit)."""
+    budget, left = args.ref_build_budget or None, seconds_left(args)
+    if left is not None:
+        if left - REF_RESERVE_S < 30:
+            raise TimeoutError("%.0f s of --full-seconds %.0f left: too little for the reference's index build (--full-seconds 0 lifts the allowance)"
+                               % (left, args.full_seconds))
+        budget = min(budget or float("inf"), left - REF_RESERVE_S)
+    return budget
 
 
 def self_spawn(args):
@@ -139,29 +169,44 @@ class Leg:
         self.timed_pool = self.pool[100:]
 
 
-def run_steps(db, searcher, leg, steps, bps, depth, world, keep_last=False):
+def last_step_batches(steps, bps, nb):
+    """Pool batch indices of the last of `steps` steps, in the order the step submitted them."""
+    return [((steps - 1) * bps + j) % nb for j in range(bps)]
+
+
+def run_steps(db, searcher, leg, steps, bps, depth, world, keep=None):
     """`steps` steps of `bps` batches each.  N = 1: through xgm_get_mset_batch_begin / xgm_batch_end with up to `depth` batches in flight,
     every batch's hits and headers delivered to pinned host memory and touched there.  N > 1: the sharded protocol per batch
     (ShardedSearcher.run_descs: search, RCCL all-gather, device merge) and an asynchronous copy of the merged result to pinned host
-    memory, double-buffered.  Returns (host seconds spent inside the calls, rows delivered, bytes of the last batch on the host)."""
+    memory, double-buffered.  keep: None, "first" (N = 1: batch 0 of the last step, the parity legs' sample; N > 1: the last batch) or
+    "all" (that and every batch of the last step: --dump-outputs).  Returns (host seconds spent inside the calls, rows delivered,
+    the batch "first" keeps, {pool batch index: (hits bytes, header bytes)} of the last step's batches as they reached the host)."""
     import collections
     import torch
     from xapiand_amd import _lib
     L = _lib.lib()
     k, nb = leg.k, len(leg.batches)
-    host_s, delivered, last = 0.0, 0, None
+    host_s, delivered, kept = 0.0, 0, {}
     if world == 1:
         inflight = collections.deque()
         hp, dp = C.POINTER(_lib.Hit)(), C.POINTER(_lib.ResultHdr)()
 
-        def finish(f, keep):
+        def finish(f, keep_it):
             _lib.check(L.xgm_batch_end(f, C.byref(hp), C.byref(dp)))
             n = dp[0].n_hits + dp[BATCH - 1].n_hits                   # the rows are host memory: read them
             snap = None
-            if keep:
+            if keep_it:
                 snap = (C.string_at(hp, BATCH * k * 16), C.string_at(dp, BATCH * 32))
             L.xgm_batch_release(f)
             return n, snap
+
+        def retire():
+            f0, b0, s0 = inflight.popleft()
+            # (batch 0 of the LAST step: the oracle answers its first 128 queries)
+            n, snap = finish(f0, keep is not None and s0 == steps - 1 and (keep == "all" or b0 == 0))
+            if snap:
+                kept[b0] = snap
+            return n
         for s in range(steps):
             for j in range(bps):
                 bi = (s * bps + j) % nb
@@ -170,53 +215,55 @@ def run_steps(db, searcher, leg, steps, bps, depth, world, keep_last=False):
                 f = C.c_void_p()
                 _lib.check(L.xgm_get_mset_batch_begin(db._h, d, g, BATCH, k, C.byref(f)))
                 host_s += time.perf_counter() - h0
-                inflight.append((f, bi))
+                inflight.append((f, bi, s))
                 if len(inflight) >= depth:
-                    f0, b0 = inflight.popleft()
-                    n, snap = finish(f0, keep_last and b0 == 0 and s == steps - 1)      # (batch 0 of the LAST step: the oracle answers its first 128 queries)
-                    delivered += n
-                    last = snap or last
+                    delivered += retire()
         while inflight:
-            f0, b0 = inflight.popleft()
-            n, snap = finish(f0, keep_last and b0 == 0)
-            delivered += n
-            last = snap or last
-        return host_s, delivered, last
+            delivered += retire()
+        return host_s, delivered, kept.get(0), kept
     # sharded: results of batch i on the host while batch i + 1 runs
     slots = getattr(searcher, "_host_slots", None)
     if slots is None:
         slots = searcher._host_slots = [dict(hits=torch.empty((BATCH, k, 2), dtype=torch.float64).pin_memory(), hdrs=torch.empty((BATCH, 4), dtype=torch.float64).pin_memory(),
                                              ev=torch.cuda.Event()) for _ in range(2)]
-    pending = [False, False]
+    pending = [None, None]          # (step, pool batch index) of the batch whose copy is in flight in each slot
+
+    def collect(sl, s0, b0):        # (after the slot's event: its rows are on the host)
+        if keep == "all" and s0 == steps - 1:
+            kept[b0] = (sl["hits"].numpy().tobytes(), sl["hdrs"].numpy().tobytes())
     i = 0
     for s in range(steps):
         for j in range(bps):
-            d, g = leg.batches[(s * bps + j) % nb]
+            bi = (s * bps + j) % nb
+            d, g = leg.batches[bi]
             sl = slots[i & 1]
             if pending[i & 1]:
                 sl["ev"].synchronize()
                 delivered += int(sl["hdrs"][0, 0].item() != -1.0)
+                collect(sl, *pending[i & 1])
             h0 = time.perf_counter()
             oh, od = searcher.run_descs(d, g, BATCH, k, slot=i & 1)        # (two sets of device buffers: batch i + 1 is enqueued while batch i's copy is in flight)
             sl["hits"].copy_(oh, non_blocking=True)
             sl["hdrs"].copy_(od, non_blocking=True)
             sl["ev"].record()
             host_s += time.perf_counter() - h0
-            pending[i & 1] = True
+            pending[i & 1] = (s, bi)
             i += 1
     for b in range(2):
         if pending[b]:
             slots[b]["ev"].synchronize()
+            collect(slots[b], *pending[b])
     last = None
-    if keep_last and i:
+    if keep and i:
         # the LAST timed batch as it reached the host: (pool batch index, merged hits [BATCH][k][2] f64 views of xgm_hit, headers)
         sl = slots[(i - 1) & 1]
         last = ((steps * bps - 1) % nb, sl["hits"].clone(), sl["hdrs"].clone())
-    return host_s, delivered, last
+    return host_s, delivered, last, kept
 
 
-def measure(db, searcher, leg, args, world, rank, dev, steps, warmup):
-    """Timed region + per-launch byte counts of one workload.  Returns a dict (rank 0 uses it; every rank takes part in the collectives)."""
+def measure(db, searcher, leg, args, world, rank, dev, steps, warmup, full=True, keep="first"):
+    """Timed region + (full) per-launch byte counts of one workload.  `keep`: what run_steps keeps of the last timed step.  Returns a dict
+    (rank 0 uses it; every rank takes part in the collectives)."""
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -239,10 +286,10 @@ def measure(db, searcher, leg, args, world, rank, dev, steps, warmup):
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    db.set_profiling(1)
+    db.set_profiling(1)             # (kernel events ride on the timed launches in every run: the timed region is the same with and without --full)
     L.xgm_debug_host_ns((C.c_uint64 * 8)())           # reset the host-side section timers
     t0 = time.perf_counter()
-    host_s, delivered, last = run_steps(db, searcher, leg, steps, bps, depth, world, keep_last=True)
+    host_s, delivered, last, kept = run_steps(db, searcher, leg, steps, bps, depth, world, keep=keep)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -257,14 +304,21 @@ def measure(db, searcher, leg, args, world, rank, dev, steps, warmup):
                      "stage_enqueue_launch": round(hn[2] / 1e3 / n_launch, 1), "staging_memcpy": round(hn[4] / 1e3 / n_launch, 1),
                      "upload_enqueue": round(hn[5] / 1e3 / n_launch, 1), "match_launch": round(hn[6] / 1e3 / n_launch, 1),
                      "merge_launch": round(hn[7] / 1e3 / n_launch, 1), "launches_per_batch": round(n_launch / n_batches_run, 2), "unit": "us per batch"}
-    kernel_ms = db.last_kernel_ms()            # mean match-kernel duration over the timed launches (HIP events on the launch streams)
-    kernel_name = db.last_kernel_name()
+    if full:
+        kernel_ms = db.last_kernel_ms()            # mean match-kernel duration over the timed launches (HIP events on the launch streams)
+        kernel_name = db.last_kernel_name()
     db.set_profiling(0)
     cdev = dev if (world == 1 or dist.get_backend() == "nccl") else torch.device("cpu")      # where the small collectives of this script live
     t = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
+    out = {"value": steps * bps * BATCH / elapsed, "unit": "queries/s", "ms_per_step": elapsed / steps * 1e3, "ms_per_batch": elapsed / n_batches_run * 1e3,
+           "queries_per_step": bps * BATCH, "steps": steps, "elapsed_s": elapsed,
+           "host_ms_per_batch": round(1e3 * host_s / n_batches_run, 4), "host_us_per_batch": host_sections,
+           "hits_delivered_to_host": True, "rows_read_on_host": delivered, "_snapshot": last, "_kept": kept}
+    if not full:
+        return out
     # the last delivered batch against a synchronous search of the same batch: the rows on the host are the answer
     verified = None
     if world == 1 and last is not None:
@@ -354,7 +408,6 @@ def measure(db, searcher, leg, args, world, rank, dev, steps, warmup):
             per_rank.append({"rank": r, "kernel_ms": ms, "bytes_per_launch": by, "basis": "model (this rank's own request tallies)",
                              "achieved": (by / (ms * 1e-3) / 1e9) if ms > 0 else None, "frac": (by / (ms * 1e-3) / HBM_PEAK) if ms > 0 else None})
 
-    n_queries = steps * bps * BATCH
     kt = kernel_ms * 1e-3 if kernel_ms and kernel_ms > 0 else None
     basis = "pmc" if traffic else ("model" if model_bytes else "algorithmic")
     moved = traffic if traffic else (model_bytes if model_bytes else bytes_per_launch)
@@ -386,11 +439,8 @@ def measure(db, searcher, leg, args, world, rank, dev, steps, warmup):
         roofline["aggregate"] = {"achieved": sum(p["achieved"] for p in ok), "peak": HBM_PEAK / 1e9 * world, "unit": "GB/s",
                                  "frac": (sum(p["frac"] for p in ok) / len(ok)) if ok else None,
                                  "note": "sum over the ranks of bytes moved per launch / that rank's kernel time; frac = mean of the per-rank fractions"}
-    return {"value": n_queries / elapsed, "unit": "queries/s", "ms_per_step": elapsed / steps * 1e3, "ms_per_batch": elapsed / n_batches_run * 1e3,
-            "queries_per_step": bps * BATCH, "steps": steps, "elapsed_s": elapsed,
-            "host_ms_per_batch": round(1e3 * host_s / n_batches_run, 4), "host_us_per_batch": host_sections,
-            "hits_delivered_to_host": True, "rows_read_on_host": delivered, "last_batch_on_host_equals_synchronous_search": verified,
-            "_snapshot": last, "roofline": roofline}
+    out.update(last_batch_on_host_equals_synchronous_search=verified, roofline=roofline)
+    return out
 
 
 def snapshot_rows(snap, k, n):
@@ -402,6 +452,36 @@ def snapshot_rows(snap, k, n):
         hits = [struct.unpack_from("<IId", snap[0], (q * k + j) * 16) for j in range(nh)]
         out.append(([(d, w) for d, _, w in hits], (nh, ms, mx, ma)))
     return out
+
+
+DUMP_LIMIT = 64 << 20       # bytes --dump-outputs may write
+
+
+def dump_outputs(path, kept, order, k):
+    """--dump-outputs: the rows the last timed step handed to its caller (xgm_batch_end's hits and headers; N > 1: the merged rows), one
+    row per query in submission order, as float64 .npy files.  Slots past a query's n_hits are written as 0.  Should the step's rows exceed
+    DUMP_LIMIT, a fixed seeded sample of its queries is written instead (query_index says which)."""
+    import numpy as np
+    hit_t = np.dtype([("docid", "<u4"), ("subqs_matched", "<u4"), ("weight", "<f8")])
+    hdr_t = np.dtype([("n_hits", "<u4"), ("max_weight_subqs_matched", "<u4"), ("matches_exact", "<u8"), ("max_attained", "<f8"), ("max_possible", "<f8")])
+    hits = np.concatenate([np.frombuffer(kept[b][0], hit_t).reshape(BATCH, k) for b in order])
+    hdrs = np.concatenate([np.frombuffer(kept[b][1], hdr_t) for b in order])
+    qidx = np.concatenate([100 + b * BATCH + np.arange(BATCH) for b in order])        # (the query's place in the leg's pool)
+    row_bytes = 8 * (3 * k + 8)
+    if len(qidx) * row_bytes > DUMP_LIMIT:
+        rows = np.sort(np.random.default_rng(QUERY_SEED).choice(len(qidx), DUMP_LIMIT // row_bytes, replace=False))
+        hits, hdrs, qidx = hits[rows], hdrs[rows], qidx[rows]
+    valid = np.arange(k)[None, :] < hdrs["n_hits"][:, None]
+    count = hdrs["matches_exact"] & np.uint64((1 << 63) - 1)
+    arrays = {"query_index": qidx, "docid": np.where(valid, hits["docid"], 0), "weight": np.where(valid, hits["weight"], 0.0),
+              "subqs_matched": np.where(valid, hits["subqs_matched"], 0), "n_hits": hdrs["n_hits"],
+              "max_weight_subqs_matched": hdrs["max_weight_subqs_matched"], "matches": count,
+              "matches_lower_bound": hdrs["matches_exact"] >> np.uint64(63),            # (1: `matches` is a lower bound, include/xgm.h)
+              "max_attained": hdrs["max_attained"], "max_possible": hdrs["max_possible"]}
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return sorted(arrays)
 
 
 def parity_vs_port(db, leg, n=128, snapshot=None, ora=None):
@@ -602,7 +682,7 @@ def sharded_cpu_baseline(args, leg, world, k):
         dirs = []
         for sh in range(world):
             d = os.path.join(tmp, "shard%d" % sh)
-            ref_index.build(d, per_shard * world, nopos=True, vocab=args.vocab, n_shards=world, shard=sh, budget_s=args.ref_build_budget or None)
+            ref_index.build(d, per_shard * world, nopos=True, vocab=args.vocab, n_shards=world, shard=sh, budget_s=ref_budget(args))
             dirs.append(d)
         build_s = time.time() - t0
         qf1, qfp = os.path.join(tmp, "q1.txt"), os.path.join(tmp, "qp.txt")
@@ -676,20 +756,24 @@ def main():
     leg = Leg(searcher, args.op, args.terms, args.required, k, n_docs_global, args.vocab, n_pool_batches,
               replay=((_lib.XGM_REPLAY_BATCH_FROZEN if ("frozen" in args.replay and args.op == "PHRASE") else 0) |
                       (_lib.XGM_REPLAY_BATCH_COUNT if "count" in args.replay else 0)))
-    m = measure(db, searcher, leg, args, world, rank, dev, args.steps, args.warmup)
+    m = measure(db, searcher, leg, args, world, rank, dev, args.steps, args.warmup, full=args.full,
+                keep="all" if args.dump_outputs else "first" if args.full else None)
     n_timed = len(leg.timed_pool)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, m.pop("_kept"), last_step_batches(args.steps, args.batches_per_step, n_pool_batches), k)
 
     # ---- N > 1: one timed batch against Xapiand's protocol on the oracle (every rank takes part) --------------------
     sharded_checked = None
-    if world > 1 and m.get("_snapshot") is not None:
+    if args.full and world > 1 and m.get("_snapshot") is not None:
         sharded_checked = sharded_parity(db, leg, world, rank, k, m["_snapshot"])
 
     # ---- every OTHER timed region of the default line next — C2 with ProtoMSet's count, C3, C5 and C5's two other modes — before the legs that
     # change the process's state (one-query latency, the server threads, the oracle on the host, the one-query-per-call modes): measured, a sub-leg
     # taken after the headline's latency leg runs 5-10 % below the same leg alone (C5 418 k against 466 k queries/s)
     headline = world == 1 and args.op == "AND" and args.terms == 3 and k == 10
+    other_configs = args.full and rank == 0 and headline and not args.no_other_configs
     early_count, early_timed, early_errors = None, {}, {}
-    if rank == 0 and headline and not args.no_other_configs:
+    if other_configs:
         FROZEN, COUNT = _lib.XGM_REPLAY_BATCH_FROZEN, _lib.XGM_REPLAY_BATCH_COUNT
         try:
             lgc = Leg(searcher, args.op, args.terms, args.required, k, n_docs_global, args.vocab, n_pool_batches, replay=COUNT)
@@ -712,16 +796,16 @@ def main():
                 early_errors[name] = repr(e)
 
     # ---- planning cost (inside every timed step): host microseconds per query ------------------------------------
-    plan_us = L.xgm_debug_plan_us(db._h, leg.batches[0][0], leg.batches[0][1], BATCH, 20)
+    plan_us = L.xgm_debug_plan_us(db._h, leg.batches[0][0], leg.batches[0][1], BATCH, 20) if args.full else None
 
     # ---- latency mode: one query in flight, host-timed around plan + search incl. H2D/D2H ---------------------
     lat = []
-    if (rank == 0 or world > 1) and not args.no_latency:
+    if args.full and (rank == 0 or world > 1) and not args.no_latency:
         lat = latency_leg(db, leg, n_timed)
 
     # ---- server mode: T host threads, each with ONE query in flight (Xapiand's http_client_pool shape) ----------
     server = None
-    if rank == 0 and world == 1 and args.threads > 0:
+    if args.full and rank == 0 and world == 1 and args.threads > 0:
         server = server_leg(db, leg.descs, leg.gstats, k, args.threads, n_timed)
 
     result = None
@@ -747,15 +831,16 @@ def main():
                                ("%d x (xgm_get_mset_batch_device + all-gather of the shards' top-k + xgm_merge_shards_device, 256 queries) with the merged hits "
                                 "copied to pinned HOST memory, double-buffered" % args.batches_per_step)},
             "ms_per_batch": m["ms_per_batch"], "host_ms_per_batch": m["host_ms_per_batch"], "host_us_per_batch": m["host_us_per_batch"],
-            "hits_delivered_to_host": m["hits_delivered_to_host"], "last_batch_on_host_equals_synchronous_search": m["last_batch_on_host_equals_synchronous_search"],
-            "p50_latency_us": lat[len(lat) // 2] * 1e6 if lat else None,
-            "p99_latency_us": lat[int(len(lat) * 0.99)] * 1e6 if lat else None,
-            "plan_us_per_query": plan_us,
+            "hits_delivered_to_host": m["hits_delivered_to_host"],
             "index": {"postings": info.n_postings, "blocks": info.n_blocks, "payload_bytes": info.payload_bytes,
                       "device_bytes": info.device_bytes, "bytes_per_posting": info.device_bytes / max(1, info.n_postings),
                       "build_seconds": build_s},
-            "roofline": m["roofline"],
         }
+        if args.full:
+            result.update({"last_batch_on_host_equals_synchronous_search": m["last_batch_on_host_equals_synchronous_search"],
+                           "p50_latency_us": lat[len(lat) // 2] * 1e6 if lat else None,
+                           "p99_latency_us": lat[int(len(lat) * 0.99)] * 1e6 if lat else None,
+                           "plan_us_per_query": plan_us, "roofline": m["roofline"]})
         if server:
             result["server_mode"] = server
         if world == 1:
@@ -764,7 +849,7 @@ def main():
                                    "packed top-k records + a device merge per batch: their N = 1 point is THIS path, not the sharded one)" % args.in_flight)
 
     # ---- C2 with the reference's known_matching_docs (the exact HTTP total) for every query: XGM_REPLAY_BATCH_COUNT inside the batch ----
-    if rank == 0 and headline and not args.no_other_configs:
+    if other_configs:
         try:
             if early_count is None:
                 raise RuntimeError(early_errors.get("exact_bounds_mode", "not measured"))
@@ -796,7 +881,7 @@ def main():
             result["exact_bounds_mode"] = {"error": repr(e)}
 
     # ---- the other single-GPU configurations of BASELINE.json in the same run: C3 (5-term OR, top-100), C5 (2-3-term PHRASE, top-10) ----
-    if rank == 0 and headline and not args.no_other_configs:
+    if other_configs:
         others = {}
         FROZEN, COUNT = _lib.XGM_REPLAY_BATCH_FROZEN, _lib.XGM_REPLAY_BATCH_COUNT
         # (their timed regions: measured above, right after the headline's)
@@ -861,14 +946,15 @@ def main():
                 result["%s_kernel_ms" % name.lower()] = oc["roofline"]["kernel_ms"]
 
     # ---- CPU baseline: the real reference + the oracle port, on this box's host cores -------------------------
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(db, leg.timed_pool, args, k, leg.timed_plans, result, m.get("_snapshot"))
     if rank == 0 and world > 1:
-        result["parity_checked_queries"] = sharded_checked
-        result["parity_against"] = "Xapiand's per-shard protocol on oracle/xgm_oracle.cc (every rank its own shard with the merged statistics; unshard + merge), the LAST TIMED batch's rows as delivered to the host"
+        if args.full:
+            result["parity_checked_queries"] = sharded_checked
+            result["parity_against"] = "Xapiand's per-shard protocol on oracle/xgm_oracle.cc (every rank its own shard with the merged statistics; unshard + merge), the LAST TIMED batch's rows as delivered to the host"
         result["n_ranks_seen"] = dist.get_world_size()
         result["code_path"] = "sharded (xgm_get_mset_batch_device + one all-gather of packed records + xgm_merge_shards_packed_device per batch, double-buffered)"
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             result["cpu_baseline"] = sharded_cpu_baseline(args, leg, world, k)
     if rank == 0:
         print(json.dumps(result), flush=True)
@@ -988,7 +1074,10 @@ def hook_parity_leg(args, tmp, dbdir, ref_docs, pools, has_positions):
         leg_name = "%s_%s" % (name, mode)
         labels[leg_name] = label
         flags += ["--leg", "%s:%s:%s" % (leg_name, mode, qf)]
-    for r in run_hook_b1(flags + ["-"], None, dbdir):
+    left = seconds_left(args)
+    if left is not None and left < 30:
+        return {"skipped": "%.0f s of --full-seconds %.0f left (--full-seconds 0 lifts the allowance)" % (left, args.full_seconds)}
+    for r in run_hook_b1(flags + ["-"], None, dbdir, timeout=1500 if left is None else min(1500, left - 15)):
         name = r.pop("leg", "error")
         out["shapes"][labels.get(name, name)] = r
         if r.get("queries") and r.get("hook_seconds"):
@@ -1098,7 +1187,7 @@ def reference_leg(args, sample, k, n_required, full, ora_full, hook_pools=None, 
     tmp = tempfile.mkdtemp(prefix="xgm_ref_", dir="/dev/shm" if os.path.isdir("/dev/shm") and os.access("/dev/shm", os.W_OK) else None)
     try:
         dbdir = os.path.join(tmp, "glass")
-        binfo = ref_index.build(dbdir, ref_docs, nopos=not with_positions, vocab=args.vocab, budget_s=args.ref_build_budget or None)
+        binfo = ref_index.build(dbdir, ref_docs, nopos=not with_positions, vocab=args.vocab, budget_s=ref_budget(args))
         qfile = os.path.join(tmp, "q.txt")
         H.write_queries(qfile, [dict(q, first=0, maxitems=k) for q in sample])
         cores = max(1, os.cpu_count() or 1)

@@ -15,7 +15,7 @@ import helpers as H  # noqa: E402
 from xapiand_amd import _lib, enquire  # noqa: E402
 
 user = sys.argv[1:]
-sys.argv = ["bench.py", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-latency", "--threads", "0"] + user
+sys.argv = ["bench.py", "--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-latency", "--threads", "0"] + user
 L = _lib.lib()
 L.xgm_debug_last_units2.restype = C.c_int64
 L.xgm_debug_last_units2.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.c_uint64]

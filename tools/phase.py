@@ -4,7 +4,7 @@ sys.path.insert(0, ROOT)
 os.environ["XGM_PHASE_TIMING"] = "1"
 import bench
 from xapiand_amd import _lib
-sys.argv = ["bench.py", "--steps", "8", "--warmup", "2", "--no-cpu-baseline"] + sys.argv[1:]
+sys.argv = ["bench.py", "--full", "--steps", "8", "--warmup", "2", "--no-cpu-baseline"] + sys.argv[1:]
 # run the bench main, then fetch phase cycles
 import io, contextlib
 buf = io.StringIO()

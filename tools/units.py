@@ -13,7 +13,7 @@ import numpy as np  # noqa: E402
 import bench  # noqa: E402
 from xapiand_amd import _lib, enquire  # noqa: E402
 
-sys.argv = ["bench.py", "--steps", "4", "--warmup", "1", "--no-cpu-baseline"] + sys.argv[1:]
+sys.argv = ["bench.py", "--full", "--steps", "4", "--warmup", "1", "--no-cpu-baseline"] + sys.argv[1:]
 L = _lib.lib()
 L.xgm_debug_last_units.restype = C.c_int64
 L.xgm_debug_last_units.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_uint64]
