@@ -856,7 +856,8 @@ static int plan_batch(const xgm_index* idx, const xgm_query* qs, uint32_t nq, xg
         }
         if (dq[i].flags & XGM_QF_FLAT) {
             /* xgm_flat_unit: rounds of 64 postings of the lead term, whatever stripes they fall in (~3 k cycles a round: two dependent gathers;
-             * a binary search per other term that has no containers) + the unit's prologue */
+             * a binary search per other term that has no containers) + the unit's prologue.  (Fitted before the body probed in two stages:
+             * a round that nobody survives now ends after the first gather — the constants await a re-fit from unit headers) */
             double flat_others = 0;
             for (uint32_t t = 1; t < qs[i].n_terms; ++t) {
                 const uint32_t id = qs[i].terms[t].term_id;

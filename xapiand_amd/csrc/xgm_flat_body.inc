@@ -10,9 +10,10 @@
  * (MultiAndPostList::find_next_match driven by the rarest term, multiandpostlist.cc:180-207; the reference skips the other lists to
  * each of its docids just so):
  *
- *   per round   64 postings of the lead term (coalesced: 256 B of docids + 64 B of wdf bytes); for every other term the candidate's
- *               wdf + 1 — ONE byte of the container of the candidate's own stripe (offsets of the unit's stripes in LDS), or a binary
- *               search of the term's flat slice inside the unit's docid range (a few hundred entries, cache-resident); the survivors'
+ *   per round   64 postings of the lead term (coalesced: 256 B of docids + 64 B of wdf bytes; requested one round ahead); for every other term the
+ *               candidate's wdf + 1 — ONE byte of the container of the candidate's own stripe (offsets of the unit's stripes in LDS), or a binary
+ *               search of the term's flat slice inside the unit's docid range (a few hundred entries, cache-resident) — in two stages: the
+ *               rarest other term (plan position 1) for all 64, the remaining terms only in the lanes that survived it; the survivors'
  *               (narrow) document lengths; BM25 in fp64 with the reference's operation order (bm25weight.cc:170-181) summed as
  *               MultiAndPostList::get_weight does (multiandpostlist.cc:150-160); top-k as everywhere (ProtoMSet::add, msetcmp.cc:55-62).
  *   PHRASE      (positional queries that prune by weight, XGM_QF_POSPRUNE, led by a long-tail term — 199 of the 256 queries of a C5 batch, 45 % of
@@ -350,43 +351,64 @@ __device__ __forceinline__ void xgm_flat_unit(const xgm_seg_dev& seg, const xgm_
         wave_lds_fence();
     };
 
+    /* 64 postings of the lead term from i0 on: docids ascending, one wdf byte each, (PHRASE) where the positions start.  The index stays inside
+     * the unit's slice [flo[0], fhi[0]) — the lanes past its end re-read its last posting — so a request never runs past the term's array */
+    auto lead_load = [&](uint32_t i0, uint32_t& d, uint32_t& w, uint32_t& p) {
+        const uint64_t i = fbase[0] + (i0 + lane < fhi[0] ? i0 + lane : fhi[0] - 1u);
+        d = seg.flat_did[i];
+        w = (uint32_t)seg.flat_wdf[i];
+        if (PHRASE) p = seg.flat_pos[i];
+    };
     uint32_t n_rounds = 0;
+    /* the lead postings are asked for one round ahead: round r + 1's are in flight while round r probes */
+    uint32_t nx_did = 0, nx_wdf = 0, nx_ps = 0;
+    if (flo[0] < fhi[0]) lead_load(flo[0], nx_did, nx_wdf, nx_ps);
     for (uint32_t i0 = flo[0]; i0 < fhi[0] && !(LIST && pf.done); i0 += 64u) {
-        const uint32_t i = i0 + lane;
-        const bool valid = i < fhi[0];
-        /* the round's postings of the lead term: docids ascending, one wdf byte each (the arrays end with 256 sentinel bytes) */
-        const uint32_t did = seg.flat_did[fbase[0] + i];
-        uint32_t wv[kDenseT], ps[kDenseT] = {0u, 0u, 0u, 0u};
-        wv[0] = (uint32_t)seg.flat_wdf[fbase[0] + i] + 1u;
-        if (PHRASE) ps[0] = seg.flat_pos[fbase[0] + i];
+        const bool valid = i0 + lane < fhi[0];
+        const uint32_t did = nx_did;
+        uint32_t wv[kDenseT] = {nx_wdf + 1u, 1u, 1u, 1u}, ps[kDenseT] = {PHRASE ? nx_ps : 0u, 0u, 0u, 0u};
+        if (i0 + 64u < fhi[0]) lead_load(i0 + 64u, nx_did, nx_wdf, nx_ps);
         if (TALLY) { cn_aux += 80u; q_cands += fhi[0] - i0 < 64u ? fhi[0] - i0 : 64u; }
         const uint32_t x = valid ? (did >> SB) - s_begin : 0u, slot = did & (W - 1u);
-        bool present = valid;
+        /* The other terms, in two stages.  Stage A, the screen: the other term with the fewest postings — plan position 1, the plan being ascending in
+         * df (MultiAndPostList's order, xgm_plan.cc; a FILTER's unweighted leaves are merged in by df).  A round without a survivor ends there.  Stage B:
+         * the remaining terms, asked for by the screen's survivors only (together: one more dependent trip, not one per term); the other lanes
+         * request nothing.  Per term: wdf + 1 (0: the term does not index the document) and, PHRASE, where the positions start in a flat term. */
+        bool present = valid, alive = valid, none = false;
 #pragma unroll
         for (uint32_t t = 1; t < kDenseT; ++t) {
-            wv[t] = 1u;
-            if (t < T) {
+            if (t == 2u && T > 2u) { alive = present; none = __ballot(present) == 0ull; }
+            if (t < T && !none) {
+                wv[t] = 0u;
                 if (dn[t] != 0xFFFFFFFFu) {
-                    /* one byte of the container of the candidate's own stripe: wdf + 1, 0 = the term does not index the document */
+                    /* one byte of the container of the candidate's own stripe */
                     const uint32_t off = rs[t * kDenseSpg + x];
-                    wv[t] = (valid && off) ? (uint32_t)seg.dense_data[(size_t)off * 16 + (size_t)NW * 4 + slot] : 0u;
-                    if (TALLY) { cn_probe += tally_sectors(valid && off != 0u, did, 6u); cn_probe_raw += (uint32_t)__popcll(__ballot(valid && off != 0u)); }
-                } else {
-                    /* the term's flat slice of the unit's range: first entry >= did (every lane searches; the loop ends with the slowest) */
-                    uint32_t lo = flo[t], hi = fhi[t];
-                    while (__ballot(valid && lo < hi)) {
-                        const uint32_t mid = (lo + hi) >> 1;
-                        const uint32_t v = seg.flat_did[fbase[t] + (lo < hi ? mid : flo[t])];
-                        if (lo < hi) { if (v < did) lo = mid + 1u; else hi = mid; }
+                    const bool ask = alive && off != 0u;
+                    if (ask) wv[t] = (uint32_t)seg.dense_data[(size_t)off * 16 + (size_t)NW * 4 + slot];
+                    if (TALLY) {
+                        /* distinct sectors among the lanes that ask (docids ascending): one per first asking lane that falls into it */
+                        const uint64_t am = __ballot(ask), below = am & ((1ull << lane) - 1ull);
+                        const uint32_t prev = (uint32_t)__shfl((int)did, below ? 63 - (int)__builtin_clzll(below) : (int)lane);
+                        cn_probe += (uint32_t)__popcll(__ballot(ask && (below == 0ull || (prev >> 6) != (did >> 6))));
+                        cn_probe_raw += (uint32_t)__popcll(am);
                     }
-                    const bool found = valid && lo < fhi[t] && seg.flat_did[fbase[t] + (lo < fhi[t] ? lo : flo[t])] == did;
-                    wv[t] = found ? (uint32_t)seg.flat_wdf[fbase[t] + lo] + 1u : 0u;
-                    if (PHRASE) ps[t] = found ? seg.flat_pos[fbase[t] + lo] : 0u;
+                } else {
+                    /* the term's flat slice of the unit's range: first entry >= did (the loop ends with the slowest lane) */
+                    uint32_t lo = alive ? flo[t] : fhi[t], hi = fhi[t];
+                    while (__ballot(lo < hi)) {
+                        const uint32_t mid = (lo + hi) >> 1;
+                        if (lo < hi) { if (seg.flat_did[fbase[t] + mid] < did) lo = mid + 1u; else hi = mid; }
+                    }
+                    if (lo < fhi[t] && seg.flat_did[fbase[t] + lo] == did) {
+                        wv[t] = (uint32_t)seg.flat_wdf[fbase[t] + lo] + 1u;
+                        if (PHRASE) ps[t] = seg.flat_pos[fbase[t] + lo];
+                    }
                     if (TALLY) { cn_aux += 16u; }
                 }
                 present = present && wv[t] != 0u;
             }
         }
+        if (none) continue;
         const uint64_t pm = __ballot(present);
         if (!PHRASE) matches += present ? 1u : 0u;                 /* (positional: a match once its positions pass) */
         if (pm == 0ull) continue;
