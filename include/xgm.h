@@ -489,6 +489,64 @@ int xgm_search_collapsed_batch(xgm_index* idx, const xgm_query* qs, uint32_t nq,
                                uint32_t collapse_max, uint32_t k_stride, xgm_hit* hits, uint32_t* hit_ord, uint32_t* hit_collapse_ord,
                                uint32_t* hit_collapse_count, xgm_result_hdr* hdrs, uint64_t* collapsed_lower_bound);
 
+/* ---- value-range filters over attached columns -------------------------------------------------------------------------------
+ * Query(OP_FILTER, q, OP_VALUE_RANGE / OP_VALUE_GE / OP_VALUE_LE ...) — Xapiand's single-valued `_range` — on the device.  A column's
+ * ordinal is 1 + the bytewise rank of the value, the order ValueRangePostList compares in (matcher/valuerangepostlist.cc:
+ * begin <= v && v <= end on the raw bytes), so a range clause is an interval of ordinals; a document without a value (ordinal 0) never
+ * matches, as in the reference, whose value list skips it.  The range node weighs nothing (get_weight / get_maxpart 0): under OP_FILTER or
+ * OP_AND it changes neither a surviving document's weight bits nor max_possible.
+ * Replaces: ValueRangePostList / ValueGePostList under OP_FILTER as the optimiser builds them (api/queryinternal.cc:1146-1271). */
+#define XGM_MAX_RANGES 4
+#define XGM_ORD_MAX 0xFFFFFFFFu
+typedef struct {
+    uint32_t slot;                        /* value slot of an attached column                                  */
+    uint32_t lo_ord, hi_ord;              /* lo_ord <= ordinal <= hi_ord; lo_ord >= 1, hi_ord may be XGM_ORD_MAX, lo_ord > hi_ord: nothing passes */
+    uint32_t reserved;
+} xgm_value_range;
+typedef struct xgm_filter xgm_filter;     /* opaque, immutable once built */
+
+/* The byte bounds of OP_VALUE_RANGE (begin, end) / OP_VALUE_GE (begin, XGM_RANGE_NO_END) / OP_VALUE_LE (empty begin, end) as an interval
+ * of ordinals of a column file (xgm_glass_export_column), by binary search over its distinct values: *lo_ord = 1 + the index of the first
+ * value >= begin (1 for an empty begin), *hi_ord = the number of values <= end, or XGM_ORD_MAX with XGM_RANGE_NO_END (end is then
+ * ignored).  begin > end gives lo_ord > hi_ord.  Host only: no device needed, works beside an index opened with XGM_DEVICE_NONE.  A caller
+ * that attached ordinals from memory (xgm_index_attach_column_ordinals) computes the interval from its own values.
+ * Replaces: the string comparisons of ValueRangePostList::next / skip_to per candidate document. */
+#define XGM_RANGE_NO_END 1u
+int xgm_column_ord_range(const char* column_path, const char* begin, size_t begin_len, const char* end, size_t end_len, uint32_t flags,
+                         uint32_t* lo_ord, uint32_t* hi_ord);
+
+/* Build on the device the set of documents that pass EVERY one of n_ranges (1 .. XGM_MAX_RANGES) clauses, one bit per document: a kernel
+ * streams the clauses' columns once (4 bytes per document and clause in, one bit per document out).  Synchronous: the filter is complete
+ * on return, immutable, and usable by any thread for any number of searches until xgm_filter_free.  *n_docs (may be NULL) = the documents
+ * passing.  XGM_UNSUPPORTED when a slot has no column attached; XGM_E_INVALID for n_ranges 0 or above XGM_MAX_RANGES or a lo_ord of 0;
+ * XGM_E_NO_DEVICE on an index without a device.  The filter belongs to the index's lastdocid (and to the columns as they were when it
+ * was built): another revision needs another filter.
+ * Replaces: one ValueRangePostList per clause walking the slot's value stream (matcher/valuerangepostlist.cc). */
+int xgm_filter_build(xgm_index*, const xgm_value_range* ranges, uint32_t n_ranges, xgm_filter** out, uint64_t* n_docs);
+/* The bitmap on the host: bit d & 31 of words[d >> 5] is set when document d passes; n_words = ceil((lastdocid + 1) / 32).  Bit 0 of word 0
+ * (docid 0) and the bits beyond lastdocid are clear.  For tests, and for a hook that wants to see where n_docs came from. */
+int xgm_filter_read(const xgm_filter*, uint32_t* words, uint32_t n_words);
+void xgm_filter_free(xgm_filter*);
+
+/* xgm_search_sorted / xgm_search_sorted_spy for Query(OP_FILTER, q, range_1 AND ... AND range_n): the documents of q that the filter lets
+ * through, under the given sort (sort == NULL: by relevance), with a ValueCountMatchSpy on spy_slot when spy_slot >= 0 (counts / n_counts
+ * as for xgm_search_sorted_spy; ignored otherwise).  Every query shape xgm_search_sorted takes.  hdr->matches_exact counts the filtered
+ * match, max_attained / max_weight_subqs_matched are those of the filtered match, the spy sees exactly the filtered match; max_possible is
+ * the unfiltered plan's (a range node's maxpart is 0).  A filter built for another lastdocid is XGM_E_INVALID.
+ * NOT reproduced: xgm_mset_bounds* for a filtered search are not specified — the reference's bounds would need
+ * ValueRangePostList::get_termfreq_min / _est / _max and the slot's value-bound statistics, which the segment does not hold.
+ * A collapse key together with a filter is not offered.
+ * Replaces: ValueRangePostList under OP_FILTER inside the matcher's main loop (api/queryinternal.cc:1146-1271, matcher/matcher.cc:482-536). */
+int xgm_search_filtered(xgm_index*, const xgm_query*, const xgm_filter*, const xgm_sort_spec* sort /* NULL = relevance */,
+                        xgm_hit* hits, uint32_t* hit_ord, xgm_result_hdr* hdr,
+                        int32_t spy_slot /* < 0 = none */, uint32_t* counts, uint32_t n_counts);
+/* nq such searches under ONE filter and ONE sort in one launch (the layout of xgm_search_sorted_batch / xgm_search_sorted_spy_batch:
+ * hits and hit_ord [nq][k_stride], hdrs [nq], counts [nq][n_counts]); the same answers as xgm_search_filtered for each. */
+int xgm_search_filtered_batch(xgm_index*, const xgm_query* qs, uint32_t nq, const xgm_filter*,
+                              const xgm_sort_spec* sort, uint32_t k_stride,
+                              xgm_hit* hits, uint32_t* hit_ord, xgm_result_hdr* hdrs,
+                              int32_t spy_slot, uint32_t* counts, uint32_t n_counts);
+
 /* EVERY matching document of a planned query — no page, no pruning — in ASCENDING DOCID order, each with its weight and the number
  * of weighted leaves matching it: the sequence the reference's matcher loop is shown by its posting-list tree (Matcher::get_local_mset,
  * matcher/matcher.cc:482-536) before ProtoMSet, the collapser, the spies or a cut-off look at it.  The plan's first / maxitems /

@@ -94,6 +94,15 @@ class SortSpec(C.Structure):
 XGM_SORT_VALUE, XGM_SORT_VALUE_RELEVANCE, XGM_SORT_RELEVANCE_VALUE = 1, 2, 3
 
 
+class ValueRange(C.Structure):
+    _fields_ = [("slot", C.c_uint32), ("lo_ord", C.c_uint32), ("hi_ord", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+XGM_MAX_RANGES = 4
+XGM_ORD_MAX = 0xFFFFFFFF
+XGM_RANGE_NO_END = 1
+
+
 class Hit(C.Structure):
     _fields_ = [("docid", C.c_uint32), ("subqs_matched", C.c_uint32), ("weight", C.c_double)]
 
@@ -122,6 +131,13 @@ _API = [
     ("xgm_search_sorted_spy", C.c_int, [C.c_void_p, _P(Query), _P(SortSpec), _P(Hit), _P(C.c_uint32), _P(ResultHdr), C.c_uint32, _P(C.c_uint32), C.c_uint32]),
     ("xgm_search_collapsed_batch", C.c_int, [C.c_void_p, _P(Query), C.c_uint32, _P(SortSpec), C.c_uint32, C.c_uint32, C.c_uint32, _P(Hit), _P(C.c_uint32),
                                     _P(C.c_uint32), _P(C.c_uint32), _P(ResultHdr), _P(C.c_uint64)]),
+    ("xgm_column_ord_range", C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_uint32, _P(C.c_uint32), _P(C.c_uint32)]),
+    ("xgm_filter_build", C.c_int, [C.c_void_p, _P(ValueRange), C.c_uint32, _P(C.c_void_p), _P(C.c_uint64)]),
+    ("xgm_filter_read", C.c_int, [C.c_void_p, _P(C.c_uint32), C.c_uint32]),
+    ("xgm_filter_free", None, [C.c_void_p]),
+    ("xgm_search_filtered", C.c_int, [C.c_void_p, _P(Query), C.c_void_p, _P(SortSpec), _P(Hit), _P(C.c_uint32), _P(ResultHdr), C.c_int32, _P(C.c_uint32), C.c_uint32]),
+    ("xgm_search_filtered_batch", C.c_int, [C.c_void_p, _P(Query), C.c_uint32, C.c_void_p, _P(SortSpec), C.c_uint32, _P(Hit), _P(C.c_uint32), _P(ResultHdr),
+                                   C.c_int32, _P(C.c_uint32), C.c_uint32]),
     ("xgm_segment_refresh_from_glass", C.c_int, [C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_char_p]),
     ("xgm_glass_export_raw", C.c_int, [C.c_char_p, C.c_char_p]),
     ("xgm_glass_info", C.c_int, [C.c_char_p, _P(C.c_uint64), _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint64)]),

@@ -1672,6 +1672,22 @@ struct ScratchRelease {
     }
 };
 
+/* A value-range filter (include/xgm.h: xgm_filter_build): the bitmap of xgm_filter_mark_kernel in HBM, never written again */
+struct xgm_filter {
+    int device = -1;
+    uint32_t lastdocid = 0;
+    uint32_t n_words = 0, n_words_padded = 0;    /* ceil((lastdocid + 1) / 32); that rounded up to XGM_FILTER_PAD_WORDS */
+    uint32_t* d_bits = nullptr;
+    uint64_t n_docs = 0;
+};
+
+static int filter_usable(const xgm_index* idx, const xgm_filter* flt) {
+    if (flt->device != idx->device || flt->lastdocid != idx->hdr.lastdocid)
+        return xgm_set_error(XGM_E_INVALID, "filter built for device %d, %u documents; index on device %d, %u documents", flt->device, flt->lastdocid, idx->device,
+                             idx->hdr.lastdocid);
+    return XGM_OK;
+}
+
 namespace {
 struct DeviceBuffers {                       /* freed on every way out */
     std::vector<void*> p;
@@ -1692,12 +1708,14 @@ struct DeviceBuffers {                       /* freed on every way out */
  * counts and the collapsed lower bound.  sort == NULL: by relevance. */
 static int sorted_core(xgm_index* idx, const xgm_query* q, const xgm_sort_spec* sort, xgm_hit* hits, uint32_t* hit_ord, xgm_result_hdr* hdr,
                        int spy_slot, uint32_t* counts, uint32_t n_counts,
-                       int collapse_slot = -1, uint32_t cmax = 0, uint32_t* hit_cord = nullptr, uint32_t* hit_ccount = nullptr, uint64_t* collapsed_lb = nullptr) {
+                       int collapse_slot = -1, uint32_t cmax = 0, uint32_t* hit_cord = nullptr, uint32_t* hit_ccount = nullptr, uint64_t* collapsed_lb = nullptr,
+                       const xgm_filter* flt = nullptr) {
     if (!idx || !q || !hits || !hdr) return xgm_set_error(XGM_E_INVALID, "null argument");
     if (idx->device == XGM_DEVICE_NONE) return xgm_set_error(XGM_E_NO_DEVICE, "index opened without a device");
     if (sort && (sort->sort_by < XGM_SORT_VALUE || sort->sort_by > XGM_SORT_RELEVANCE_VALUE)) return xgm_set_error(XGM_E_INVALID, "sort_by %u", sort->sort_by);
-    if (!sort && collapse_slot < 0 && spy_slot < 0) return xgm_set_error(XGM_E_INVALID, "neither a sort nor a collapse key nor a spy");
+    if (!sort && collapse_slot < 0 && spy_slot < 0 && !flt) return xgm_set_error(XGM_E_INVALID, "neither a sort nor a collapse key nor a spy");
     if (collapse_slot >= 0 && (cmax == 0 || spy_slot >= 0)) return xgm_set_error(XGM_E_INVALID, "collapse_max 0, or a spy together with a collapse key");
+    if (flt) if (int frc = filter_usable(idx, flt)) return frc;
     const uint32_t mode = sort ? sort->sort_by : 4u;
     const bool reverse = sort && sort->reverse;
     const uint32_t* d_ord = nullptr;
@@ -1768,7 +1786,9 @@ static int sorted_core(xgm_index* idx, const xgm_query* q, const xgm_sort_spec* 
     L.tab_terms = bp.tab_terms; L.cap = bp.cap; L.k_stride = k;
     L.phrase = bp.phrase; L.wide = bp.wide; L.sided = 0;
     L.cand = nullptr; L.ghdr = d_ghdr;
-    if ((rc = xgm_launch_match_sorted(L, d_ord, mode, reverse ? 1u : 0u, d_spy_ord, d_counts, d_cord, cmax, d_cand, stream))) return rc;
+    if ((rc = xgm_launch_match_sorted(L, d_ord, mode, reverse ? 1u : 0u, d_spy_ord, d_counts, d_cord, cmax, d_cand, stream, nullptr, nullptr, nullptr, 0,
+                                      flt ? flt->d_bits : nullptr)))
+        return rc;
     HIP_TRY(hipMemcpyAsync(hb + o_gh, sc->d_sorted + o_gh, total - o_gh, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     const xgm_group_hdr* gh = (const xgm_group_hdr*)(hb + o_gh);
@@ -1840,10 +1860,12 @@ extern "C" int xgm_search_sorted(xgm_index* idx, const xgm_query* q, const xgm_s
  * matches per collapse key — the spy mechanism on the collapse column, one row per query — give the collapse counts and lower bounds */
 static int sorted_batch_core(xgm_index* idx, const xgm_query* qs, uint32_t nq, const xgm_sort_spec* sort, uint32_t k_stride, xgm_hit* hits,
                              uint32_t* hit_ord, xgm_result_hdr* hdrs, int spy_slot, uint32_t* counts, uint32_t n_counts,
-                             int collapse_slot = -1, uint32_t cmax = 0, uint32_t* hit_cord = nullptr, uint32_t* hit_ccount = nullptr, uint64_t* collapsed_lb = nullptr) {
+                             int collapse_slot = -1, uint32_t cmax = 0, uint32_t* hit_cord = nullptr, uint32_t* hit_ccount = nullptr, uint64_t* collapsed_lb = nullptr,
+                             const xgm_filter* flt = nullptr) {
     if (!idx || !qs || !hits || !hdrs || nq == 0) return xgm_set_error(XGM_E_INVALID, "null argument");
-    if (!sort && collapse_slot < 0 && spy_slot < 0) return xgm_set_error(XGM_E_INVALID, "neither a sort nor a collapse key nor a spy");
+    if (!sort && collapse_slot < 0 && spy_slot < 0 && !flt) return xgm_set_error(XGM_E_INVALID, "neither a sort nor a collapse key nor a spy");
     if (idx->device == XGM_DEVICE_NONE) return xgm_set_error(XGM_E_NO_DEVICE, "index opened without a device");
+    if (flt) if (int frc = filter_usable(idx, flt)) return frc;
     if (sort && (sort->sort_by < XGM_SORT_VALUE || sort->sort_by > XGM_SORT_RELEVANCE_VALUE)) return xgm_set_error(XGM_E_INVALID, "sort_by %u", sort->sort_by);
     if (collapse_slot >= 0 && (cmax == 0 || spy_slot >= 0)) return xgm_set_error(XGM_E_INVALID, "collapse_max 0, or a spy together with a collapse key");
     const uint32_t mode = sort ? sort->sort_by : 4u;
@@ -1916,7 +1938,9 @@ static int sorted_batch_core(xgm_index* idx, const xgm_query* qs, uint32_t nq, c
     L.cand = nullptr; L.ghdr = (xgm_group_hdr*)(sc->d_sorted + o_gh);
     idx->last_kernel = "xgm_match_sorted_kernel";
     L.spy_stride = d_counts ? n_counts : 0u;
-    if ((rc = xgm_launch_match_sorted(L, d_ord, mode, reverse ? 1u : 0u, d_spy_ord, d_counts, d_cord, d_cord ? cmax : 0u, (xgm_cand_sorted*)(sc->d_sorted + o_cd), stream))) return rc;
+    if ((rc = xgm_launch_match_sorted(L, d_ord, mode, reverse ? 1u : 0u, d_spy_ord, d_counts, d_cord, d_cord ? cmax : 0u, (xgm_cand_sorted*)(sc->d_sorted + o_cd), stream,
+                                      nullptr, nullptr, nullptr, 0, flt ? flt->d_bits : nullptr)))
+        return rc;
     HIP_TRY(hipMemcpyAsync(hb + o_gh, sc->d_sorted + o_gh, total - o_gh, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     if (d_counts) memcpy(counts, hb + o_ct, b_ct);
@@ -2009,6 +2033,124 @@ extern "C" int xgm_search_collapsed(xgm_index* idx, const xgm_query* q, const xg
                                     xgm_hit* hits, uint32_t* hit_ord, uint32_t* hit_collapse_ord, uint32_t* hit_collapse_count, xgm_result_hdr* hdr,
                                     uint64_t* collapsed_lower_bound) {
     return sorted_core(idx, q, sort, hits, hit_ord, hdr, -1, nullptr, 0, (int)collapse_slot, collapse_max, hit_collapse_ord, hit_collapse_count, collapsed_lower_bound);
+}
+
+/* ---- value-range filters (include/xgm.h: xgm_filter_build, xgm_search_filtered) ---------------------------------------------
+ * A clause is an interval of a column's ordinals; xgm_filter_mark_kernel (xgm_filter.h) turns up to XGM_MAX_RANGES of them into one bit per
+ * document, and the sorted searches above drop the matching documents whose bit is clear (xgm_match_sorted_kernel, fbits). */
+
+extern "C" int xgm_column_ord_range(const char* column_path, const char* begin, size_t begin_len, const char* end, size_t end_len, uint32_t flags,
+                                    uint32_t* lo_ord, uint32_t* hi_ord) {
+    if (!column_path || !lo_ord || !hi_ord || (begin_len && !begin) || (!(flags & XGM_RANGE_NO_END) && end_len && !end)) return xgm_set_error(XGM_E_INVALID, "null argument");
+    if (flags & ~XGM_RANGE_NO_END) return xgm_set_error(XGM_E_INVALID, "flags %u", flags);
+    FILE* f = fopen(column_path, "rb");
+    if (!f) return xgm_set_error(XGM_E_IO, "cannot open %s: %s", column_path, strerror(errno));
+    char magic[8];
+    uint32_t h32[4];
+    std::vector<uint64_t> off;
+    std::vector<char> bytes;
+    bool ok = fread(magic, 1, 8, f) == 8 && fread(h32, 4, 4, f) == 4 && memcmp(magic, "XGMCOL1", 8) == 0;
+    ok = ok && fseek(f, (long)(((size_t)h32[1] + 1) * 4), SEEK_CUR) == 0;              /* (the ordinals) */
+    if (ok) { off.resize((size_t)h32[2] + 1); ok = fread(off.data(), 8, off.size(), f) == off.size(); }
+    for (size_t i = 0; ok && i + 1 < off.size(); ++i) ok = off[i] <= off[i + 1];
+    if (ok) { ok = off[0] == 0; bytes.resize((size_t)off.back()); ok = ok && fread(bytes.data(), 1, bytes.size(), f) == bytes.size(); }
+    fclose(f);
+    if (!ok) return xgm_set_error(XGM_E_INVALID, "%s is not a column file", column_path);
+    const uint32_t n = h32[2];
+    /* bytewise order, a prefix before its extensions: std::string's and ValueRangePostList's */
+    auto cmp = [&](uint32_t i, const char* key, size_t key_len) {
+        const size_t len = (size_t)(off[i + 1] - off[i]), m = std::min(len, key_len);
+        const int c = m ? memcmp(bytes.data() + off[i], key, m) : 0;
+        return c ? c : (len < key_len ? -1 : len > key_len ? 1 : 0);
+    };
+    uint32_t a = 0, b = n;                         /* first value >= begin */
+    while (a < b) { const uint32_t mid = a + (b - a) / 2; if (cmp(mid, begin, begin_len) < 0) a = mid + 1; else b = mid; }
+    *lo_ord = a + 1u;
+    if (flags & XGM_RANGE_NO_END) { *hi_ord = XGM_ORD_MAX; return XGM_OK; }
+    a = 0; b = n;                                  /* first value > end = the number of values <= end */
+    while (a < b) { const uint32_t mid = a + (b - a) / 2; if (cmp(mid, end, end_len) <= 0) a = mid + 1; else b = mid; }
+    *hi_ord = a;
+    return XGM_OK;
+}
+
+extern "C" int xgm_filter_build(xgm_index* idx, const xgm_value_range* ranges, uint32_t n_ranges, xgm_filter** out, uint64_t* n_docs) {
+    if (!idx || !ranges || !out) return xgm_set_error(XGM_E_INVALID, "null argument");
+    *out = nullptr;
+    if (idx->device == XGM_DEVICE_NONE) return xgm_set_error(XGM_E_NO_DEVICE, "index opened without a device");
+    if (n_ranges == 0 || n_ranges > XGM_MAX_RANGES) return xgm_set_error(XGM_E_INVALID, "%u range clauses (1 .. %d)", n_ranges, XGM_MAX_RANGES);
+    xgm_filter_clauses cl = {};
+    cl.n = n_ranges;
+    for (uint32_t c = 0; c < n_ranges; ++c) {
+        if (ranges[c].lo_ord == 0) return xgm_set_error(XGM_E_INVALID, "range clause %u: lo_ord 0 (ordinals start at 1)", c);
+        cl.lo[c] = ranges[c].lo_ord; cl.hi[c] = ranges[c].hi_ord;
+    }
+    {
+        std::lock_guard<std::mutex> lk(idx->columns_mu);
+        for (uint32_t c = 0; c < n_ranges; ++c) {
+            auto it = idx->columns.find(ranges[c].slot);
+            if (it == idx->columns.end()) return XGM_UNSUPPORTED;
+            cl.ord[c] = (const uint32_t*)it->second.first;
+        }
+    }
+    int rc = use_device(idx->device);
+    if (rc) return rc;
+    const uint64_t n_bits = (uint64_t)idx->hdr.lastdocid + 1u;
+    const uint32_t n_words = (uint32_t)((n_bits + 31u) / 32u);
+    const uint32_t n_padded = (uint32_t)(((uint64_t)n_words + XGM_FILTER_PAD_WORDS - 1u) / XGM_FILTER_PAD_WORDS * XGM_FILTER_PAD_WORDS);
+    XgmScratch* sc;
+    if ((rc = scratch_acquire(idx, &sc))) return rc;
+    ScratchRelease release_{idx, sc};
+    DeviceBuffers tmp;
+    unsigned long long* d_count = nullptr;
+    if ((rc = tmp.alloc((void**)&d_count, 8))) return rc;
+    uint32_t* d_bits = nullptr;
+    HIP_TRY(hipMalloc((void**)&d_bits, (size_t)n_padded * 4));
+    unsigned long long count = 0;
+    hipError_t e = hipMemsetAsync(d_count, 0, 8, sc->stream);
+    if (e == hipSuccess) {
+        rc = xgm_launch_filter_mark(cl, idx->hdr.lastdocid, n_padded, d_bits, d_count, sc->stream);
+        if (rc) { hipStreamSynchronize(sc->stream); hipFree(d_bits); return rc; }
+        e = hipMemcpyAsync(&count, d_count, 8, hipMemcpyDeviceToHost, sc->stream);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(sc->stream);
+    if (e != hipSuccess) { hipStreamSynchronize(sc->stream); hipFree(d_bits); return xgm_launch_error("filter build", (int)e, hipGetErrorString(e)); }
+    xgm_filter* flt = new xgm_filter();
+    flt->device = idx->device; flt->lastdocid = idx->hdr.lastdocid;
+    flt->n_words = n_words; flt->n_words_padded = n_padded;
+    flt->d_bits = d_bits; flt->n_docs = count;
+    if (n_docs) *n_docs = count;
+    *out = flt;
+    return XGM_OK;
+}
+
+extern "C" int xgm_filter_read(const xgm_filter* flt, uint32_t* words, uint32_t n_words) {
+    if (!flt || !words) return xgm_set_error(XGM_E_INVALID, "null argument");
+    if (n_words != flt->n_words) return xgm_set_error(XGM_E_INVALID, "%u words for a filter of %u", n_words, flt->n_words);
+    int rc = use_device(flt->device);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(words, flt->d_bits, (size_t)n_words * 4, hipMemcpyDeviceToHost));
+    return XGM_OK;
+}
+
+extern "C" void xgm_filter_free(xgm_filter* flt) {
+    if (!flt) return;
+    if (use_device(flt->device) == XGM_OK) hipFree(flt->d_bits);
+    delete flt;
+}
+
+extern "C" int xgm_search_filtered(xgm_index* idx, const xgm_query* q, const xgm_filter* flt, const xgm_sort_spec* sort, xgm_hit* hits, uint32_t* hit_ord,
+                                   xgm_result_hdr* hdr, int32_t spy_slot, uint32_t* counts, uint32_t n_counts) {
+    if (!flt) return xgm_set_error(XGM_E_INVALID, "null argument");
+    const bool spy = spy_slot >= 0;
+    return sorted_core(idx, q, sort, hits, hit_ord, hdr, spy ? (int)spy_slot : -1, spy ? counts : nullptr, spy ? n_counts : 0u, -1, 0, nullptr, nullptr, nullptr, flt);
+}
+
+extern "C" int xgm_search_filtered_batch(xgm_index* idx, const xgm_query* qs, uint32_t nq, const xgm_filter* flt, const xgm_sort_spec* sort, uint32_t k_stride,
+                                         xgm_hit* hits, uint32_t* hit_ord, xgm_result_hdr* hdrs, int32_t spy_slot, uint32_t* counts, uint32_t n_counts) {
+    if (!flt) return xgm_set_error(XGM_E_INVALID, "null argument");
+    const bool spy = spy_slot >= 0;
+    return sorted_batch_core(idx, qs, nq, sort, k_stride, hits, hit_ord, hdrs, spy ? (int)spy_slot : -1, spy ? counts : nullptr, spy ? n_counts : 0u, -1, 0, nullptr, nullptr,
+                             nullptr, flt);
 }
 
 /* ---- every match of a query, in docid order (include/xgm.h: xgm_search_all) -------------------------------------------------

@@ -37,6 +37,7 @@
 #include "xgm_launch.h"
 #include "xgm_wave.h"
 #include "xgm_posfilter.h"
+#include "xgm_filter.h"
 
 namespace {
 
@@ -2404,7 +2405,8 @@ size_t xgm_match_sorted_smem_bytes(uint32_t stripe_bits, uint32_t tab_terms, boo
 
 int xgm_launch_match_sorted(const xgm_match_launch& L, const uint32_t* ord, uint32_t mode, uint32_t reverse, const uint32_t* spy_ord, uint32_t* spy_counts,
                             const uint32_t* cord, uint32_t cmax, xgm_cand_sorted* cand, hipStream_t stream,
-                            unsigned long long* all_keys, unsigned long long* all_vals, unsigned long long* all_count, unsigned long long all_cap) {
+                            unsigned long long* all_keys, unsigned long long* all_vals, unsigned long long* all_count, unsigned long long all_cap,
+                            const uint32_t* fbits) {
     dim3 grid(L.n_work), block(XGM_WG);
     if (L.sub_bits > L.seg.stripe_bits || L.seg.stripe_bits - L.sub_bits < 8u) return xgm_launch_error("sorted match kernel", 0, "bad sub-stripe width");
     const size_t smem = xgm_match_sorted_smem_bytes(L.seg.stripe_bits - L.sub_bits, L.tab_terms, L.phrase, L.cap, L.wide, L.stripes_per_group);
@@ -2419,7 +2421,7 @@ int xgm_launch_match_sorted(const xgm_match_launch& L, const uint32_t* ord, uint
         if (int rc_ = ensure_dyn_smem(kern, smem, seen)) return rc_;                                         \
         hipLaunchKernelGGL(kern, grid, block, smem, stream, L.seg, L.queries, L.work, L.stripes_per_group,     \
                            L.tab_terms, L.cap, L.k_stride, ord, mode, reverse, spy_ord, spy_counts, cord, cmax, cand, L.ghdr, \
-                           all_keys, all_vals, all_count, all_cap, L.sub_bits, L.spy_stride);                  \
+                           all_keys, all_vals, all_count, all_cap, L.sub_bits, L.spy_stride, fbits);           \
     } while (0)
     if (L.wide) { if (L.phrase) XGM_LAUNCH(uint16_t, true); else XGM_LAUNCH(uint16_t, false); }
     else { if (L.phrase) XGM_LAUNCH(uint8_t, true); else XGM_LAUNCH(uint8_t, false); }

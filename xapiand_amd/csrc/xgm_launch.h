@@ -52,7 +52,19 @@ size_t xgm_match_sorted_smem_bytes(uint32_t stripe_bits, uint32_t tab_terms, boo
 int xgm_launch_match_sorted(const xgm_match_launch& L, const uint32_t* ord, uint32_t mode, uint32_t reverse, const uint32_t* spy_ord, uint32_t* spy_counts,
                             const uint32_t* cord, uint32_t cmax, xgm_cand_sorted* cand, hipStream_t stream,
                             unsigned long long* all_keys = nullptr, unsigned long long* all_vals = nullptr, unsigned long long* all_count = nullptr,
-                            unsigned long long all_cap = 0);
+                            unsigned long long all_cap = 0, const uint32_t* fbits = nullptr);
+/* fbits != NULL (xgm_search_filtered*): a bitmap of xgm_launch_filter_mark over this segment's documents — a matching document whose bit is clear
+ * is dropped before it is counted, weighed against the best weight, shown to the spy, listed or offered to the top k */
+/* value-range filters (xgm_filter.h): the bitmap of the documents every clause lets through — bit d & 31 of word d >> 5, n_words_padded words
+ * (a multiple of XGM_FILTER_PAD_WORDS covering lastdocid + 1 bits), all of them written; *count (device, zeroed by the caller) receives the set bits */
+#define XGM_FILTER_PAD_WORDS 64u
+struct xgm_filter_clauses {
+    const uint32_t* ord[XGM_MAX_RANGES];     /* device columns, [lastdocid + 1] */
+    uint32_t lo[XGM_MAX_RANGES], hi[XGM_MAX_RANGES];
+    uint32_t n;
+};
+int xgm_launch_filter_mark(const xgm_filter_clauses& cl, uint32_t lastdocid, uint32_t n_words_padded, uint32_t* bits, unsigned long long* count,
+                           hipStream_t stream);
 /* all_keys != NULL (xgm_search_all): every matching document is also appended, in no particular order, to all_keys / all_vals
  * (docid << 32 | weighted leaves matched, weight bits) at the position the zeroed counter *all_count hands out; entries beyond all_cap
  * are counted, not written.  xgm_all_order_pack (xgm_all.hip) restores docid order: tmp = xgm_all_order_bytes(lastdocid) device bytes. */

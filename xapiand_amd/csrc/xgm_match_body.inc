@@ -16,7 +16,8 @@ __global__ __launch_bounds__(XGM_WG) void xgm_match_sorted_kernel(xgm_seg_dev se
                                                                    xgm_group_hdr* __restrict__ ghdr_out,
                                                                    unsigned long long* __restrict__ all_keys, unsigned long long* __restrict__ all_vals,
                                                                    unsigned long long* __restrict__ all_count, unsigned long long all_cap,
-                                                                   uint32_t sub_bits, uint32_t spy_stride) {
+                                                                   uint32_t sub_bits, uint32_t spy_stride,
+                                                                   const uint32_t* __restrict__ fbits) {
 #else
 __global__ __launch_bounds__(XGM_WG) void xgm_match_kernel(xgm_seg_dev seg, const xgm_dev_query* __restrict__ queries,
                                                             const xgm_work* __restrict__ work, uint32_t stripes_per_group,
@@ -339,6 +340,11 @@ __global__ __launch_bounds__(XGM_WG) void xgm_match_kernel(xgm_seg_dev seg, cons
                 const bool list_fail = phrase && !pass && all_keys && (q.flags & XGM_QF_LIST_CONJ);
 #else
                 const bool list_fail = false;
+#endif
+#if XGM_BODY_SORTED
+                /* xgm_search_filtered: a document the value-range filter's bitmap (xgm_filter.h) leaves out does not match — ValueRangePostList
+                 * under OP_FILTER; the range weighs 0.0, so the others keep their weight bits */
+                if (fbits && !((fbits[did >> 5] >> (did & 31u)) & 1u)) pass = false;
 #endif
                 if (pass || list_fail) {
                     if (pass) ++my_matches;

@@ -239,6 +239,15 @@ class Database:
             raise Unsupported("no column attached for value slot %d" % slot)
         return vals
 
+    def build_filter(self, ranges):
+        """xgm_filter_build: the documents whose ordinals pass EVERY (slot, lo_ord, hi_ord) of `ranges` (1 .. 4 clauses on attached columns;
+        column_ord_range makes the ordinals from byte bounds), as a bitmap on the device → Filter."""
+        n = len(ranges)
+        arr = (_lib.ValueRange * max(1, n))(*[_lib.ValueRange(s, lo, hi, 0) for s, lo, hi in ranges])
+        h, nd = C.c_void_p(), C.c_uint64()
+        _lib.check(_lib.lib().xgm_filter_build(self._h, arr, n, C.byref(h), C.byref(nd)))
+        return Filter(h, nd.value, (self._info.lastdocid + 32) // 32)
+
     def set_stream(self, hip_stream):
         _lib.check(_lib.lib().xgm_index_set_stream(self._h, C.c_void_p(hip_stream)))
 
@@ -255,6 +264,30 @@ class Database:
 
     def last_kernel_name(self):
         return (_lib.lib().xgm_last_kernel_name(self._h) or b"").decode()
+
+
+class Filter:
+    """A value-range filter on the device (Database.build_filter): immutable; n_docs = the documents it lets through."""
+
+    def __init__(self, handle, n_docs, n_words):
+        self._h, self.n_docs, self._n_words = handle, n_docs, n_words
+
+    def words(self):
+        """xgm_filter_read: the bitmap as a list of 32-bit words, bit d & 31 of word d >> 5 set when document d passes."""
+        w = (C.c_uint32 * self._n_words)()
+        _lib.check(_lib.lib().xgm_filter_read(self._h, w, self._n_words))
+        return list(w)
+
+    def close(self):
+        if self._h:
+            _lib.lib().xgm_filter_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class MSetItem:
@@ -454,6 +487,52 @@ def search_sorted_spy(db, planned, sort_by, slot, reverse, spy_slot, n_distinct)
     spec = _lib.SortSpec(sort_by, slot, 1 if reverse else 0, 0)
     _lib.check(_lib.lib().xgm_search_sorted_spy(db._h, C.byref(planned), C.byref(spec), hits, ords, C.byref(hdr), spy_slot, counts, n_distinct + 1))
     return [(hits[i].docid, hits[i].weight, hits[i].subqs_matched, ords[i]) for i in range(hdr.n_hits)], hdr, list(counts)
+
+
+def column_ord_range(path, begin, end):
+    """xgm_column_ord_range: the byte bounds of OP_VALUE_RANGE (begin, end) / OP_VALUE_GE (begin, None) / OP_VALUE_LE (b"", end) as the
+    interval (lo_ord, hi_ord) of a column file's ordinals; host only."""
+    b = _as_bytes(begin) if begin else b""
+    e = b"" if end is None else _as_bytes(end)
+    lo, hi = C.c_uint32(), C.c_uint32()
+    _lib.check(_lib.lib().xgm_column_ord_range(_as_bytes(path), b, len(b), e, len(e), _lib.XGM_RANGE_NO_END if end is None else 0, C.byref(lo), C.byref(hi)))
+    return lo.value, hi.value
+
+
+def _spy_args(spy):
+    """spy = None | (spy_slot, n_distinct) → (slot argument, counters per query)"""
+    return (-1, 0) if spy is None else (spy[0], spy[1] + 1)
+
+
+def search_filtered(db, planned, flt, sort_by=None, slot=0, reverse=False, spy=None):
+    """xgm_search_filtered: Query(OP_FILTER, planned, the filter's ranges) under a value sort (sort_by 1 / 2 / 3 on `slot`) or by relevance
+    (sort_by None); spy = (spy_slot, n_distinct) adds a ValueCountMatchSpy.  Returns ([(docid, weight, subqs, ordinal)], hdr, counts or None)."""
+    k = max(1, planned.first + planned.maxitems)
+    hits = (_lib.Hit * k)()
+    ords = (C.c_uint32 * k)()
+    hdr = _lib.ResultHdr()
+    spec = _lib.SortSpec(sort_by, slot, 1 if reverse else 0, 0) if sort_by else None
+    spy_slot, nc = _spy_args(spy)
+    counts = (C.c_uint32 * nc)() if nc else None
+    _lib.check(_lib.lib().xgm_search_filtered(db._h, C.byref(planned), flt._h, C.byref(spec) if spec else None, hits, ords, C.byref(hdr), spy_slot, counts, nc))
+    return [(hits[i].docid, hits[i].weight, hits[i].subqs_matched, ords[i]) for i in range(hdr.n_hits)], hdr, (list(counts) if nc else None)
+
+
+def search_filtered_batch(db, plans, flt, sort_by=None, slot=0, reverse=False, spy=None):
+    """xgm_search_filtered_batch: every planned query under ONE filter and one sort (or relevance) in one launch →
+    [([(docid, weight, subqs, ordinal)], hdr, counts or None)]."""
+    nq = len(plans)
+    ks = max(1, max(p.first + p.maxitems for p in plans))
+    qs = (_lib.Query * nq)(*plans)
+    hits = (_lib.Hit * (nq * ks))()
+    ords = (C.c_uint32 * (nq * ks))()
+    hdrs = (_lib.ResultHdr * nq)()
+    spec = _lib.SortSpec(sort_by, slot, 1 if reverse else 0, 0) if sort_by else None
+    spy_slot, nc = _spy_args(spy)
+    counts = (C.c_uint32 * (nq * nc))() if nc else None
+    _lib.check(_lib.lib().xgm_search_filtered_batch(db._h, qs, nq, flt._h, C.byref(spec) if spec else None, ks, hits, ords, hdrs, spy_slot, counts, nc))
+    return [([(hits[q * ks + i].docid, hits[q * ks + i].weight, hits[q * ks + i].subqs_matched, ords[q * ks + i]) for i in range(hdrs[q].n_hits)], hdrs[q],
+             (list(counts[q * nc:(q + 1) * nc]) if nc else None)) for q in range(nq)]
 
 
 def search_collapsed(db, planned, collapse_slot, collapse_max, sort_by=None, slot=0, reverse=False):
