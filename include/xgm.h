@@ -714,6 +714,17 @@ int64_t xgm_debug_read_doclen(xgm_index*, uint32_t* out, uint64_t cap);
  * their number (0 when the segment has no positions) or < 0. */
 int64_t xgm_debug_read_positions(xgm_index*, uint32_t term_id, uint32_t* out, uint64_t cap);
 
+/* Diagnostics: copy the probe container of (term, stripe) to the host: u32 bits[W/32] (presence), u8 wdf1[W] (wdf + 1, 0 = absent), on an
+ * index with positions u32 pos_base[W/64] (position-entry offset, relative to the term, of each 64-slot bucket's first posting; 0xFFFFFFFF for
+ * an empty bucket), u32 bits2[W/32] (wdf >= 2).  layout[4]: W, byte offset of pos_base (0: none), byte offset of bits2, the term's largest
+ * wdf as the planner knows it.  Returns the bytes copied, 0 when the term has no containers or none in this stripe, or < 0.  Launches no kernel. */
+int64_t xgm_debug_read_container(xgm_index*, uint32_t term_id, uint32_t stripe, unsigned char* out, uint64_t cap, uint32_t* layout);
+
+/* Diagnostics: copy a term's flat posting arrays to the host: docids, wdf bytes and, into pos when not NULL and the index keeps them
+ * (*has_pos = 1), each posting's position-entry offset relative to the term.  Returns the number of postings, 0 when the term has no flat
+ * array, or < 0.  Launches no kernel. */
+int64_t xgm_debug_read_flat(xgm_index*, uint32_t term_id, uint32_t* did, unsigned char* wdf, uint32_t* pos, uint64_t cap, uint32_t* has_pos);
+
 /* Diagnostics: mean host time of xgm_plan_query per query (microseconds) over `reps` passes of descs[0..nq). */
 double xgm_debug_plan_us(const xgm_index*, const xgm_query_desc* descs, const xgm_global_stats* gs, uint32_t nq, uint32_t reps);
 

@@ -3038,6 +3038,57 @@ extern "C" int64_t xgm_debug_read_positions(xgm_index* idx, uint32_t term_id, ui
     return (int64_t)n;
 }
 
+/* Copy the probe container of (term, stripe) to the host as the kernels see it: u32 bits[W/32], u8 wdf1[W], with positions u32 pos_base[W/64],
+ * u32 bits2[W/32].  layout: [0] W, [1] byte offset of pos_base (0: none), [2] byte offset of bits2, [3] the term's largest wdf as the planner
+ * knows it.  Returns the container's size in bytes, 0 when the term has no containers or none in this stripe.  Copies only: no kernel runs. */
+extern "C" int64_t xgm_debug_read_container(xgm_index* idx, uint32_t term_id, uint32_t stripe, unsigned char* out, uint64_t cap, uint32_t* layout) {
+    if (!idx || (!out && cap)) return xgm_set_error(XGM_E_INVALID, "null argument");
+    if (term_id >= idx->hdr.n_terms) return xgm_set_error(XGM_E_INVALID, "term id out of range");
+    if (stripe >= idx->view.n_stripes) return xgm_set_error(XGM_E_INVALID, "stripe out of range");
+    int rc = use_device(idx->device);
+    if (rc) return rc;
+    if (!idx->view.n_dense || !idx->d_dense_id || !idx->d_dense_dir || !idx->d_dense_data) return 0;
+    uint32_t d = 0xFFFFFFFFu, off = 0;
+    HIP_TRY(hipMemcpy(&d, (const uint32_t*)idx->d_dense_id + term_id, 4, hipMemcpyDeviceToHost));
+    if (d == 0xFFFFFFFFu) return 0;
+    if (d >= idx->view.n_dense) return xgm_set_error(XGM_E_INVALID, "dense id %u out of range", d);
+    HIP_TRY(hipMemcpy(&off, (const uint32_t*)idx->d_dense_dir + (size_t)d * idx->view.n_stripes + stripe, 4, hipMemcpyDeviceToHost));
+    if (off == 0) return 0;
+    const uint32_t W = 1u << idx->hdr.stripe_bits, NW = W / 32u;
+    const uint64_t bytes = (uint64_t)idx->view.dense_plane + (uint64_t)NW * 4u;
+    if (cap < bytes) return xgm_set_error(XGM_E_INVALID, "buffer too small");
+    HIP_TRY(hipMemcpy(out, (const unsigned char*)idx->d_dense_data + (size_t)off * 16, bytes, hipMemcpyDeviceToHost));
+    if (layout) {
+        layout[0] = W; layout[1] = idx->view.dense_pos ? NW * 4u + W : 0u; layout[2] = idx->view.dense_plane;
+        layout[3] = idx->term_wdfmax.empty() ? idx->term_wdfub[term_id] : idx->term_wdfmax[term_id];
+    }
+    return (int64_t)bytes;
+}
+
+/* Copy a term's flat posting arrays to the host: docids, wdf bytes and (pos != NULL and the index keeps them: *has_pos = 1) the position-entry offset
+ * of every posting.  Returns the number of postings, 0 when the term has no flat array.  Copies only: no kernel runs. */
+extern "C" int64_t xgm_debug_read_flat(xgm_index* idx, uint32_t term_id, uint32_t* did, unsigned char* wdf, uint32_t* pos, uint64_t cap, uint32_t* has_pos) {
+    if (!idx || ((!did || !wdf) && cap)) return xgm_set_error(XGM_E_INVALID, "null argument");
+    if (term_id >= idx->hdr.n_terms) return xgm_set_error(XGM_E_INVALID, "term id out of range");
+    int rc = use_device(idx->device);
+    if (rc) return rc;
+    if (has_pos) *has_pos = 0;
+    if (!idx->d_flat_off || !idx->d_flat_did || !idx->d_flat_wdf) return 0;
+    uint64_t o[2] = {0, 0};
+    HIP_TRY(hipMemcpy(o, (const uint64_t*)idx->d_flat_off + term_id, 16, hipMemcpyDeviceToHost));
+    if (o[1] < o[0] || o[1] > idx->flat_postings) return xgm_set_error(XGM_E_INVALID, "flat slice of term %u out of range", term_id);
+    const uint64_t n = o[1] - o[0];
+    if (n == 0) return 0;
+    if (cap < n) return xgm_set_error(XGM_E_INVALID, "buffer too small");
+    HIP_TRY(hipMemcpy(did, (const uint32_t*)idx->d_flat_did + o[0], n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(wdf, (const unsigned char*)idx->d_flat_wdf + o[0], n, hipMemcpyDeviceToHost));
+    if (pos && idx->d_flat_pos) {
+        HIP_TRY(hipMemcpy(pos, (const uint32_t*)idx->d_flat_pos + o[0], n * 4, hipMemcpyDeviceToHost));
+        if (has_pos) *has_pos = 1;
+    }
+    return (int64_t)n;
+}
+
 /* Traffic model of the LAST batch launched on this index (wave kernels, tallying instantiation: xgm_index_set_profiling
  * bit 1): the per-unit tallies of what the match kernel requested from memory, summed over the batch's work units.
  * Waits for the device.  Layout of out[0..n): include/xgm.h. */

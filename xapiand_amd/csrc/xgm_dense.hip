@@ -22,6 +22,8 @@ namespace {
 
 constexpr uint32_t kStage = 272;
 
+/* Reads s[w + 1] whatever the field needs (k_flat_fill: straight from the payload; k_dense_fill stages ngw + nww + 2 words of it): at most two words
+ * past a block's payload.  For the last block of the last term those are the XGM_WORD_PAD zero words XgmSegmentWriter::finish ends the section with. */
 __device__ __forceinline__ uint32_t dn_extract(const uint32_t* s, uint32_t idx, uint32_t bw) {
     uint32_t bit = idx * bw, w = bit >> 5;
     uint32_t v = __builtin_amdgcn_alignbit(s[w + 1], s[w], bit & 31u);

@@ -86,6 +86,8 @@ __device__ uint32_t wave_lower_bound(const uint32_t* __restrict__ arr_, uint32_t
     return lo + (uint32_t)__popcll(__ballot(less));
 }
 
+/* Reads s[w + 1] whatever the field needs, and the decoders stage two words more than a block's payload: past the last block of the last term lie the
+ * XGM_WORD_PAD zero words the segment writer ends the word section with (xgm_validate_header refuses a section without them). */
 __device__ __forceinline__ uint32_t extract_bits(const uint32_t* s, uint32_t idx, uint32_t bw) {
     uint32_t bit = idx * bw;
     uint32_t w = bit >> 5;
