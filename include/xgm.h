@@ -547,6 +547,35 @@ int xgm_search_filtered_batch(xgm_index*, const xgm_query* qs, uint32_t nq, cons
                               xgm_hit* hits, uint32_t* hit_ord, xgm_result_hdr* hdrs,
                               int32_t spy_slot, uint32_t* counts, uint32_t n_counts);
 
+/* Query(OP_VALUE_RANGE / OP_VALUE_GE / OP_VALUE_LE) or an AND of up to XGM_MAX_RANGES of them as the WHOLE query — no text, only the
+ * restriction, what a dashboard sends with a sort by a date or a key and `_aggregations` over another field: the documents of the filter,
+ * k = first + maxitems of them (1 .. XGM_MAX_K; the caller drops the first `first`, and pages by asking for the largest k).
+ * Every weight of a range-only tree is 0 (ValueRangePostList::get_weight / get_maxpart), so max_possible is 0 and the matcher rewrites the
+ * ordering (matcher/matcher.cc:415-430): by relevance becomes ascending docid; by value then relevance and by relevance then value become by
+ * value, then ascending docid.  Hence
+ *   sort == NULL                            the first k documents of the filter in ascending docid order
+ *   XGM_SORT_VALUE, XGM_SORT_VALUE_RELEVANCE, XGM_SORT_RELEVANCE_VALUE (all three the same answer)
+ *                                           the first k under (value, docid ascending) in xgm_search_sorted's value order: the smaller
+ *                                           ordinal first and ordinal 0 (no value) before all; with `reverse` the larger ordinal first and
+ *                                           ordinal 0 last; ascending docid breaks ties in both directions.
+ * hits[i].weight is +0.0.  hits[i].subqs_matched is 0: the field counts WEIGHTED leaves and there are none (ValueRangePostList::
+ * count_matching_subqs returns 1 per clause, but with max_possible == 0 every percentage is 100 and nothing reads it).  hit_ord[i] (may be
+ * NULL) = the hit's ordinal in the sort slot, 0 without a sort.  hdr->n_hits = min(k, the filter's n_docs), hdr->matches_exact = n_docs,
+ * max_attained = max_possible = 0, max_weight_subqs_matched = 0.
+ * spy_slot >= 0: a ValueCountMatchSpy as in xgm_search_sorted_spy — counts[o] = the passing documents whose ordinal in spy_slot is o,
+ * n_counts = that column's distinct values + 1, the counts sum to matches_exact (counts / n_counts are ignored when spy_slot < 0).  They are
+ * those of EVERY passing document; under docid order the reference stops once the page is full (stop_once_full, matcher.cc:467-470), so
+ * its own spy sees only a prefix: a hook that needs the reference's counts keeps such a search on the CPU.
+ * XGM_E_INVALID: a null idx / flt / hits / hdr, k == 0 or k > XGM_MAX_K, a filter built for another index, an n_counts that is not the
+ * spy column's; XGM_UNSUPPORTED: the sort or spy slot has no column attached.  Safe from any number of threads on one index and one filter.
+ * NOT offered: a collapse key; xgm_mset_bounds* (the reason given for xgm_search_filtered); descending docid order (set_docid_order); a batch
+ * form (one filter has one answer); shards; Query::MatchAll without a filter.  The matcher hook does not lower such queries yet.
+ * Replaces: ValueRangePostList as the root of the posting-list tree walked by the matcher's main loop (matcher/matcher.cc:482-536). */
+int xgm_search_range(xgm_index*, const xgm_filter*, const xgm_sort_spec* sort /* NULL = docid order */,
+                     uint32_t k /* first + maxitems, 1 .. XGM_MAX_K */,
+                     xgm_hit* hits, uint32_t* hit_ord /* may be NULL */, xgm_result_hdr* hdr,
+                     int32_t spy_slot /* < 0 = none */, uint32_t* counts, uint32_t n_counts);
+
 /* EVERY matching document of a planned query — no page, no pruning — in ASCENDING DOCID order, each with its weight and the number
  * of weighted leaves matching it: the sequence the reference's matcher loop is shown by its posting-list tree (Matcher::get_local_mset,
  * matcher/matcher.cc:482-536) before ProtoMSet, the collapser, the spies or a cut-off look at it.  The plan's first / maxitems /

@@ -138,6 +138,7 @@ _API = [
     ("xgm_search_filtered", C.c_int, [C.c_void_p, _P(Query), C.c_void_p, _P(SortSpec), _P(Hit), _P(C.c_uint32), _P(ResultHdr), C.c_int32, _P(C.c_uint32), C.c_uint32]),
     ("xgm_search_filtered_batch", C.c_int, [C.c_void_p, _P(Query), C.c_uint32, C.c_void_p, _P(SortSpec), C.c_uint32, _P(Hit), _P(C.c_uint32), _P(ResultHdr),
                                    C.c_int32, _P(C.c_uint32), C.c_uint32]),
+    ("xgm_search_range", C.c_int, [C.c_void_p, C.c_void_p, _P(SortSpec), C.c_uint32, _P(Hit), _P(C.c_uint32), _P(ResultHdr), C.c_int32, _P(C.c_uint32), C.c_uint32]),
     ("xgm_segment_refresh_from_glass", C.c_int, [C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_char_p]),
     ("xgm_glass_export_raw", C.c_int, [C.c_char_p, C.c_char_p]),
     ("xgm_glass_info", C.c_int, [C.c_char_p, _P(C.c_uint64), _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint64)]),

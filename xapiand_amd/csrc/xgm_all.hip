@@ -124,3 +124,6 @@ int xgm_all_order_pack(void* tmp, uint32_t lastdocid, const unsigned long long* 
     if (e != hipSuccess) return xgm_launch_error("xgm_search_all ordering kernels", (int)e, hipGetErrorString(e));
     return 0;
 }
+
+/* the other selection over one bit per document: a value-range filter's bitmap as the whole query (xgm_search_range) */
+#include "xgm_range.h"

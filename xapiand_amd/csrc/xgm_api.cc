@@ -2153,6 +2153,82 @@ extern "C" int xgm_search_filtered_batch(xgm_index* idx, const xgm_query* qs, ui
                              nullptr, flt);
 }
 
+/* ---- a filter as the whole query (include/xgm.h: xgm_search_range) ---------------------------------------------------------------
+ * No plan and no postings: the filter's bitmap and at most two columns are all the kernels of xgm_range.h read.  One scratch of the pool,
+ * every kernel on its stream, one copy back ([spy counters | header | hits | ordinals], contiguous in the work area) and one
+ * synchronisation; the filter and the columns are only read, so any number of threads may ask at once. */
+extern "C" int xgm_search_range(xgm_index* idx, const xgm_filter* flt, const xgm_sort_spec* sort, uint32_t k, xgm_hit* hits, uint32_t* hit_ord, xgm_result_hdr* hdr,
+                                int32_t spy_slot, uint32_t* counts, uint32_t n_counts) {
+    if (!idx || !flt || !hits || !hdr) return xgm_set_error(XGM_E_INVALID, "null argument");
+    if (k == 0 || k > XGM_MAX_K) return xgm_set_error(XGM_E_INVALID, "k %u (1 .. %d)", k, XGM_MAX_K);
+    if (idx->device == XGM_DEVICE_NONE) return xgm_set_error(XGM_E_NO_DEVICE, "index opened without a device");
+    if (int frc = filter_usable(idx, flt)) return frc;
+    if (sort && (sort->sort_by < XGM_SORT_VALUE || sort->sort_by > XGM_SORT_RELEVANCE_VALUE)) return xgm_set_error(XGM_E_INVALID, "sort_by %u", sort->sort_by);
+    xgm_range_launch L = {};
+    {
+        std::lock_guard<std::mutex> lk(idx->columns_mu);
+        if (sort) {
+            auto it = idx->columns.find(sort->slot);
+            if (it == idx->columns.end()) return XGM_UNSUPPORTED;
+            L.ord = (const uint32_t*)it->second.first;
+            L.n_distinct = it->second.second;
+            L.reverse = sort->reverse ? 1u : 0u;
+        }
+        if (spy_slot >= 0) {
+            auto it = idx->columns.find((uint32_t)spy_slot);
+            if (it == idx->columns.end()) return XGM_UNSUPPORTED;
+            if (!counts || n_counts != it->second.second + 1u) return xgm_set_error(XGM_E_INVALID, "spy: %u counters for a column of %u distinct values (+ 1 for no value)", n_counts, it->second.second);
+            L.spy_ord = (const uint32_t*)it->second.first;
+            L.n_counts = n_counts;
+        }
+    }
+    memset(hdr, 0, sizeof *hdr);
+    hdr->matches_exact = flt->n_docs;
+    if (flt->n_docs == 0) {                                        /* nothing passes: no page, a spy that saw nothing */
+        if (L.spy_ord) memset(counts, 0, (size_t)n_counts * 4);
+        return XGM_OK;
+    }
+    int rc = use_device(idx->device);
+    if (rc) return rc;
+    L.bits = flt->d_bits;
+    L.n_tiles = flt->n_words_padded / XGM_FILTER_PAD_WORDS;
+    L.lastdocid = flt->lastdocid;
+    L.k = (uint32_t)std::min<uint64_t>(k, flt->n_docs);
+    L.n_docs = flt->n_docs;
+    const xgm_range_layout y = xgm_range_work_layout(L.n_tiles, L.k, L.n_counts);
+    XgmScratch* sc;
+    if ((rc = scratch_acquire(idx, &sc))) return rc;
+    ScratchRelease release_{idx, sc};
+    const size_t down = y.o_pairs - y.o_counts;
+    if ((rc = grow(&sc->d_sorted, &sc->cap_sorted, y.total))) return rc;
+    if ((rc = grow_pinned(&sc->h_sorted, &sc->cap_hsorted, down))) return rc;
+    L.work = sc->d_sorted;
+    if (idx->profiling) {
+        std::lock_guard<std::mutex> lk(idx->scratch_mu);
+        if (idx->prof_used == idx->prof_events.size()) {
+            hipEvent_t a, b;
+            HIP_TRY(hipEventCreate(&a));
+            HIP_TRY(hipEventCreate(&b));
+            idx->prof_events.push_back({a, b});
+        }
+        L.ev_start = (hipEvent_t)idx->prof_events[idx->prof_used].first;
+        L.ev_stop = (hipEvent_t)idx->prof_events[idx->prof_used].second;
+        ++idx->prof_used;
+    }
+    idx->last_kernel = "xgm_range_place_kernel";
+    if ((rc = xgm_launch_range(L, sc->stream))) return rc;
+    unsigned char* hb = (unsigned char*)sc->h_sorted;
+    HIP_TRY(hipMemcpyAsync(hb, sc->d_sorted + y.o_counts, down, hipMemcpyDeviceToHost, sc->stream));
+    HIP_TRY(hipStreamSynchronize(sc->stream));
+    const xgm_result_hdr* dh = (const xgm_result_hdr*)(hb + (y.o_hdr - y.o_counts));
+    if (dh->n_hits != L.k) return xgm_set_error(XGM_E_DEVICE, "range search: %u hits for a page of %u", dh->n_hits, L.k);
+    if (L.spy_ord) memcpy(counts, hb, (size_t)n_counts * 4);
+    memcpy(hits, hb + (y.o_hits - y.o_counts), (size_t)L.k * sizeof(xgm_hit));
+    if (hit_ord) memcpy(hit_ord, hb + (y.o_ords - y.o_counts), (size_t)L.k * 4);
+    hdr->n_hits = L.k;
+    return XGM_OK;
+}
+
 /* ---- every match of a query, in docid order (include/xgm.h: xgm_search_all) -------------------------------------------------
  * The workgroup kernel (every query shape; it decodes the posting blocks of each stripe: K1 at full size) weighs every matching
  * document anyway when it runs under a sort; here it also appends each to one list (a wave-aggregated atomic per round), which

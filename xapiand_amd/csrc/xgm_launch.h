@@ -65,6 +65,24 @@ struct xgm_filter_clauses {
 };
 int xgm_launch_filter_mark(const xgm_filter_clauses& cl, uint32_t lastdocid, uint32_t n_words_padded, uint32_t* bits, unsigned long long* count,
                            hipStream_t stream);
+/* a filter's bitmap as the whole query (xgm_range.h, xgm_search_range): the first k passing documents by docid (ord NULL) or by (value, docid)
+ * under ord / reverse, counts of the passing documents per ordinal of spy_ord (NULL: none).  work = xgm_range_work_layout(...).total device
+ * bytes, 256-byte aligned; afterwards [o_counts, o_pairs) holds the spy counters, the header, k hits and k ordinals — one copy back. */
+struct xgm_range_launch {
+    const uint32_t* bits;             /* device, n_tiles * XGM_FILTER_PAD_WORDS words (xgm_launch_filter_mark) */
+    uint32_t n_tiles, lastdocid;
+    const uint32_t* ord;              /* device sort column [lastdocid + 1] or NULL */
+    uint32_t n_distinct, reverse;
+    const uint32_t* spy_ord;          /* device spy column or NULL */
+    uint32_t n_counts;
+    uint32_t k;                       /* 1 .. min(XGM_MAX_K, n_docs) */
+    uint64_t n_docs;                  /* the bitmap's set bits */
+    unsigned char* work;
+    hipEvent_t ev_start = nullptr, ev_stop = nullptr;      /* recorded around the kernels when set */
+};
+struct xgm_range_layout { size_t o_state, o_ghist, o_counts, o_hdr, o_hits, o_ords, o_pairs, o_tiles, b_tiles, total; };
+xgm_range_layout xgm_range_work_layout(uint32_t n_tiles, uint32_t k, uint32_t n_counts);
+int xgm_launch_range(const xgm_range_launch& L, hipStream_t stream);
 /* all_keys != NULL (xgm_search_all): every matching document is also appended, in no particular order, to all_keys / all_vals
  * (docid << 32 | weighted leaves matched, weight bits) at the position the zeroed counter *all_count hands out; entries beyond all_cap
  * are counted, not written.  xgm_all_order_pack (xgm_all.hip) restores docid order: tmp = xgm_all_order_bytes(lastdocid) device bytes. */

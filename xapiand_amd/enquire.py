@@ -535,6 +535,21 @@ def search_filtered_batch(db, plans, flt, sort_by=None, slot=0, reverse=False, s
              (list(counts[q * nc:(q + 1) * nc]) if nc else None)) for q in range(nq)]
 
 
+def search_range(db, flt, k, sort_by=None, slot=0, reverse=False, spy=None):
+    """xgm_search_range: the filter's ranges as the WHOLE query — the first k documents it lets through in ascending docid order (sort_by None)
+    or under (value of `slot`, docid) (sort_by 1 / 2 / 3: the same answer, the reference orders all three by value when every weight is 0);
+    spy = (spy_slot, n_distinct) adds a ValueCountMatchSpy.  Returns ([(docid, weight, subqs, ordinal)], hdr, counts or None)."""
+    n = max(1, k)
+    hits = (_lib.Hit * n)()
+    ords = (C.c_uint32 * n)()
+    hdr = _lib.ResultHdr()
+    spec = _lib.SortSpec(sort_by, slot, 1 if reverse else 0, 0) if sort_by else None
+    spy_slot, nc = _spy_args(spy)
+    counts = (C.c_uint32 * nc)() if nc else None
+    _lib.check(_lib.lib().xgm_search_range(db._h, flt._h, C.byref(spec) if spec else None, k, hits, ords, C.byref(hdr), spy_slot, counts, nc))
+    return [(hits[i].docid, hits[i].weight, hits[i].subqs_matched, ords[i]) for i in range(hdr.n_hits)], hdr, (list(counts) if nc else None)
+
+
 def search_collapsed(db, planned, collapse_slot, collapse_max, sort_by=None, slot=0, reverse=False):
     """xgm_search_collapsed: set_collapse_key(collapse_slot, collapse_max), ranked by relevance (sort_by None) or under a value sort.
     Returns ([(docid, weight, subqs, sort ordinal, collapse ordinal, collapse count)], hdr, collapsed lower bound)."""
