@@ -749,6 +749,11 @@ int64_t xgm_debug_read_positions(xgm_index*, uint32_t term_id, uint32_t* out, ui
  * wdf as the planner knows it.  Returns the bytes copied, 0 when the term has no containers or none in this stripe, or < 0.  Launches no kernel. */
 int64_t xgm_debug_read_container(xgm_index*, uint32_t term_id, uint32_t stripe, unsigned char* out, uint64_t cap, uint32_t* layout);
 
+/* Diagnostics: the 64-bit summary of the container's wdf bytes as the conjunction kernels see it: bit j is set iff a posting in slots
+ * [j W/64, (j + 1) W/64) of the stripe has a wdf other than 1 (0 or >= 2).  Returns 1 and sets *out; 0, *out unchanged, when the term has no container in this stripe
+ * or the index keeps no summary (XGM_NO_WDF_SUMMARY at open, or no memory for it); < 0 on error.  Launches no kernel. */
+int xgm_debug_read_wdf_summary(xgm_index*, uint32_t term_id, uint32_t stripe, uint64_t* out);
+
 /* Diagnostics: copy a term's flat posting arrays to the host: docids, wdf bytes and, into pos when not NULL and the index keeps them
  * (*has_pos = 1), each posting's position-entry offset relative to the term.  Returns the number of postings, 0 when the term has no flat
  * array, or < 0.  Launches no kernel. */

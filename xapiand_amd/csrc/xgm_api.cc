@@ -208,6 +208,7 @@ static void fill_view(xgm_index* idx) {
     v.stripe_bits = idx->hdr.stripe_bits;
     v.lastdocid = idx->hdr.lastdocid;
     v.dense_id = nullptr; v.dense_dir = nullptr; v.dense_data = nullptr; v.n_dense = 0; v.dense_pos = 0; v.dense_plane = 0;
+    v.dense_p2 = nullptr; v.bit_screen = 0;
     v.doclen_narrow = nullptr; v.doclen_narrow_bits = 0; v.doclen_base = 0;
     v.flat_off = nullptr; v.flat_did = nullptr; v.flat_wdf = nullptr; v.flat_pos = nullptr;
     v.n_stripes = (idx->hdr.lastdocid >> idx->hdr.stripe_bits) + 1u;
@@ -289,6 +290,7 @@ extern "C" void xgm_index_close(xgm_index* idx) {
     if (idx->d_flat_wdf) hipFree(idx->d_flat_wdf);
     if (idx->d_flat_pos) hipFree(idx->d_flat_pos);
     if (idx->d_dense_dir) hipFree(idx->d_dense_dir);
+    if (idx->d_dense_p2) hipFree(idx->d_dense_p2);
     if (idx->d_dense_data) hipFree(idx->d_dense_data);
     for (auto& c : idx->columns) if (c.second.first) hipFree(c.second.first);
     for (void* c : idx->retired_columns) hipFree(c);
@@ -3139,6 +3141,27 @@ extern "C" int64_t xgm_debug_read_container(xgm_index* idx, uint32_t term_id, ui
         layout[3] = idx->term_wdfmax.empty() ? idx->term_wdfub[term_id] : idx->term_wdfmax[term_id];
     }
     return (int64_t)bytes;
+}
+
+/* The wdf != 1 summary word of (term, stripe) as the kernels see it (xgm_seg_dev::dense_p2).  Returns 1 and sets *out; 0, *out unchanged, when the
+ * term has no container in this stripe or the index keeps no summary.  Copies only: no kernel runs. */
+extern "C" int xgm_debug_read_wdf_summary(xgm_index* idx, uint32_t term_id, uint32_t stripe, uint64_t* out) {
+    if (!idx || !out) return xgm_set_error(XGM_E_INVALID, "null argument");
+    if (term_id >= idx->hdr.n_terms) return xgm_set_error(XGM_E_INVALID, "term id out of range");
+    if (stripe >= idx->view.n_stripes) return xgm_set_error(XGM_E_INVALID, "stripe out of range");
+    int rc = use_device(idx->device);
+    if (rc) return rc;
+    if (!idx->view.n_dense || !idx->d_dense_id || !idx->d_dense_dir || !idx->d_dense_p2) return 0;
+    uint32_t d = 0xFFFFFFFFu, off = 0;
+    HIP_TRY(hipMemcpy(&d, (const uint32_t*)idx->d_dense_id + term_id, 4, hipMemcpyDeviceToHost));
+    if (d == 0xFFFFFFFFu) return 0;
+    if (d >= idx->view.n_dense) return xgm_set_error(XGM_E_INVALID, "dense id %u out of range", d);
+    HIP_TRY(hipMemcpy(&off, (const uint32_t*)idx->d_dense_dir + (size_t)d * idx->view.n_stripes + stripe, 4, hipMemcpyDeviceToHost));
+    if (off == 0) return 0;
+    uint64_t w = 0;
+    HIP_TRY(hipMemcpy(&w, (const uint64_t*)idx->d_dense_p2 + (size_t)d * idx->view.n_stripes + stripe, 8, hipMemcpyDeviceToHost));
+    *out = w;
+    return 1;
 }
 
 /* Copy a term's flat posting arrays to the host: docids, wdf bytes and (pos != NULL and the index keeps them: *has_pos = 1) the position-entry offset

@@ -49,10 +49,11 @@ __global__ void k_dense_count(xgm_seg_dev seg, const uint32_t* __restrict__ dens
 /* one workgroup per (stripe, dense term): decode the run, write the bitmap and the per-slot wdf+1 bytes */
 __global__ __launch_bounds__(256) void k_dense_fill(xgm_seg_dev seg, const uint32_t* __restrict__ dense_terms, uint32_t n_stripes,
                                                     const uint32_t* __restrict__ dir, unsigned char* __restrict__ data, int with_pos,
-                                                    uint32_t* __restrict__ wdf_max) {
+                                                    uint32_t* __restrict__ wdf_max, unsigned long long* __restrict__ p2) {
     __shared__ uint32_t bitmap[256];
     __shared__ uint32_t bitmap2[256];     /* wdf >= 2 */
     __shared__ uint32_t wmax_s;
+    __shared__ uint32_t sum_s[2];         /* the summary word of xgm_seg_dev::dense_p2 */
     __shared__ uint32_t pbase[128];       /* with_pos: position-entry offset (relative to the term) of the first posting of every 64-slot bucket */
     __shared__ uint32_t stage_all[4 * kStage];
     __shared__ uint32_t run[2];
@@ -65,7 +66,7 @@ __global__ __launch_bounds__(256) void k_dense_fill(xgm_seg_dev seg, const uint3
     unsigned char* cont = data + (size_t)off * 16;
     unsigned char* wdf_out = cont + (size_t)NW * 4;
     if (tid < NW) { bitmap[tid] = 0; bitmap2[tid] = 0; }
-    if (tid == 0) wmax_s = 0;
+    if (tid == 0) { wmax_s = 0; sum_s[0] = 0; sum_s[1] = 0; }
     if (tid < 128u) pbase[tid] = 0xFFFFFFFFu;
     for (uint32_t i = tid; i < W / 16u; i += 256u) reinterpret_cast<uint4*>(wdf_out)[i] = make_uint4(0, 0, 0, 0);
     if (tid == 0) {                       /* the run's blocks: binary search on the term's block firsts */
@@ -103,8 +104,8 @@ __global__ __launch_bounds__(256) void k_dense_fill(xgm_seg_dev seg, const uint3
         const uint32_t pex = with_pos ? seg.blk_pos[b] + dn_scan(lw) - lw : 0u;
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        if (v0) { const uint32_t sl = d0 & (W - 1u); atomicOr(&bitmap[sl >> 5], 1u << (sl & 31u)); if (w0 >= 2u) atomicOr(&bitmap2[sl >> 5], 1u << (sl & 31u)); wdf_out[sl] = (unsigned char)(w0 + 1u); if (with_pos) atomicMin(&pbase[sl >> 6], pex); }
-        if (v1) { const uint32_t sl = d1 & (W - 1u); atomicOr(&bitmap[sl >> 5], 1u << (sl & 31u)); if (w1 >= 2u) atomicOr(&bitmap2[sl >> 5], 1u << (sl & 31u)); wdf_out[sl] = (unsigned char)(w1 + 1u); if (with_pos) atomicMin(&pbase[sl >> 6], pex + w0); }
+        if (v0) { const uint32_t sl = d0 & (W - 1u); atomicOr(&bitmap[sl >> 5], 1u << (sl & 31u)); if (w0 >= 2u) atomicOr(&bitmap2[sl >> 5], 1u << (sl & 31u)); wdf_out[sl] = (unsigned char)(w0 + 1u); if (with_pos) atomicMin(&pbase[sl >> 6], pex); if (w0 != 1u) atomicOr(&sum_s[sl >> (SB - 1u)], 1u << ((sl >> (SB - 6u)) & 31u)); }
+        if (v1) { const uint32_t sl = d1 & (W - 1u); atomicOr(&bitmap[sl >> 5], 1u << (sl & 31u)); if (w1 >= 2u) atomicOr(&bitmap2[sl >> 5], 1u << (sl & 31u)); wdf_out[sl] = (unsigned char)(w1 + 1u); if (with_pos) atomicMin(&pbase[sl >> 6], pex + w0); if (w1 != 1u) atomicOr(&sum_s[sl >> (SB - 1u)], 1u << ((sl >> (SB - 6u)) & 31u)); }
         wmax = max(wmax, max(w0, w1));
     }
     if (wmax) atomicMax(&wmax_s, wmax);
@@ -113,6 +114,8 @@ __global__ __launch_bounds__(256) void k_dense_fill(xgm_seg_dev seg, const uint3
     if (with_pos && tid < W / 64u) reinterpret_cast<uint32_t*>(wdf_out + W)[tid] = pbase[tid];
     if (tid < NW) reinterpret_cast<uint32_t*>(wdf_out + W + (with_pos ? NW * 2u : 0u))[tid] = bitmap2[tid];
     if (tid == 0 && wmax_s) atomicMax(&wdf_max[d], wmax_s);            /* the term's true largest wdf: the disjunction's pruning bound */
+    /* 64 bits per container (xgm_seg_dev::dense_p2): bit j = a posting in slots [j W/64, (j + 1) W/64) whose wdf is not 1 (stripe_bits >= 6: a slot or more per bit) */
+    if (p2 && tid == 0) p2[(size_t)d * n_stripes + s] = (unsigned long long)sum_s[0] | ((unsigned long long)sum_s[1] << 32);
 }
 
 /* *misfit is raised when a length does not fit T above the base (a header whose bounds do not cover its own lengths): the narrow
@@ -263,7 +266,8 @@ int xgm_build_dense(xgm_index* idx) {
 
 static int build_containers(xgm_index* idx) {
     idx->view.dense_id = nullptr; idx->view.dense_dir = nullptr; idx->view.dense_data = nullptr;
-    idx->view.n_dense = 0; idx->view.dense_plane = 0;
+    idx->view.n_dense = 0; idx->view.dense_plane = 0; idx->view.dense_p2 = nullptr; idx->view.bit_screen = 0;
+    if (idx->d_dense_p2) { hipFree(idx->d_dense_p2); idx->d_dense_p2 = nullptr; }
     idx->term_wdfmax.clear();
     const uint32_t SB = idx->hdr.stripe_bits;
     const uint32_t n_stripes = (idx->hdr.lastdocid >> SB) + 1u;
@@ -315,8 +319,16 @@ static int build_containers(xgm_index* idx) {
     DN_TRY(hipMemcpy(idx->d_dense_dir, dir.data(), dir.size() * 4, hipMemcpyHostToDevice));
     DN_TRY(hipMalloc((void**)&d_wmax, (size_t)n_dense * 4));
     DN_TRY(hipMemset(d_wmax, 0, (size_t)n_dense * 4));
+    /* the wdf != 1 summary, one u64 per (dense term, stripe), 0 where there is no container.  An accelerator like the flat arrays: without the
+     * memory for it the index opens and every probe fetches its byte.  XGM_NO_WDF_SUMMARY: A/B switch for measurements */
+    if (!getenv("XGM_NO_WDF_SUMMARY")) {
+        if (hipMalloc(&idx->d_dense_p2, dir.size() * 8) != hipSuccess || hipMemset(idx->d_dense_p2, 0, dir.size() * 8) != hipSuccess) {
+            (void)hipGetLastError();
+            if (idx->d_dense_p2) { hipFree(idx->d_dense_p2); idx->d_dense_p2 = nullptr; }
+        }
+    }
     hipLaunchKernelGGL(k_dense_fill, dim3(n_stripes, n_dense), dim3(256), 0, 0, idx->view, d_terms, n_stripes, (const uint32_t*)idx->d_dense_dir,
-                       (unsigned char*)idx->d_dense_data, with_pos, d_wmax);
+                       (unsigned char*)idx->d_dense_data, with_pos, d_wmax, (unsigned long long*)idx->d_dense_p2);
     DN_TRY(hipGetLastError());
     DN_TRY(hipDeviceSynchronize());
     wmax.resize(n_dense);
@@ -324,7 +336,7 @@ static int build_containers(xgm_index* idx) {
     idx->term_wdfmax.assign(idx->term_wdfub.begin(), idx->term_wdfub.end());
     for (uint32_t d = 0; d < n_dense; ++d)
         if (wmax[d] && wmax[d] < idx->term_wdfmax[dense_terms[d]]) idx->term_wdfmax[dense_terms[d]] = wmax[d];
-    idx->dense_bytes = dense_id.size() * 4 + dir.size() * 4 + units * 16;
+    idx->dense_bytes = dense_id.size() * 4 + dir.size() * 4 + units * 16 + (idx->d_dense_p2 ? dir.size() * 8 : 0);
     idx->device_bytes += idx->dense_bytes;
     idx->view.dense_id = (const uint32_t*)idx->d_dense_id;
     idx->view.dense_dir = (const uint32_t*)idx->d_dense_dir;
@@ -332,6 +344,8 @@ static int build_containers(xgm_index* idx) {
     idx->view.n_dense = n_dense;
     idx->view.dense_pos = (uint32_t)with_pos;
     idx->view.dense_plane = plane_off;
+    idx->view.dense_p2 = (const unsigned long long*)idx->d_dense_p2;
+    idx->view.bit_screen = getenv("XGM_NO_BIT_SCREEN") ? 0u : 1u;      /* A/B switch: xgm_flat_unit screens by the wdf byte again */
     idx->dense_min_df = (uint64_t)min_avg * n_stripes;
     hipFree(d_terms); hipFree(d_cnt); hipFree(d_wmax);
     return XGM_OK;
@@ -342,5 +356,7 @@ fail:
     if (idx->d_dense_id) { hipFree(idx->d_dense_id); idx->d_dense_id = nullptr; }
     if (idx->d_dense_dir) { hipFree(idx->d_dense_dir); idx->d_dense_dir = nullptr; }
     if (idx->d_dense_data) { hipFree(idx->d_dense_data); idx->d_dense_data = nullptr; }
+    if (idx->d_dense_p2) { hipFree(idx->d_dense_p2); idx->d_dense_p2 = nullptr; }
+    idx->view.dense_p2 = nullptr;
     return rc;
 }

@@ -57,11 +57,15 @@ constexpr uint32_t kDensePipe = XGM_DENSE_PIPE;                   /* rounds of g
 constexpr uint32_t kDenseHistEvery = XGM_DENSE_HIST_EVERY;        /* rounds between two looks at the query-wide histogram (a power of two; A/B: tools/ab_build.sh) */
 constexpr uint32_t kDenseSq = 128;         /* positional survivors waiting for their test (< 64 left by a drain + <= 64 of a round) */
 
+/* top-k buffer, container offsets, candidate ring: what every instantiation keeps at the start of the slice */
+constexpr size_t kDenseCoreBytes = (size_t)kDenseCap * 8 + (size_t)kDenseCap * 4 + (size_t)kDenseT * kDenseSpg * 4 + (size_t)kDenseRing * 4;
+/* plain conjunctions: the wdf != 1 summary words (xgm_seg_dev::dense_p2) of the unit's (stripe, term) pairs, as u32 [kDenseSpg][2 halves][kDenseT] — the
+ * four terms' bits of a candidate's slot are ONE 16-byte LDS read; xgm_flat_unit keeps them as u64 [kDenseT][kDenseSpg] behind its offsets */
+constexpr size_t kDenseP2Bytes = (size_t)kDenseSpg * kDenseT * 8;
 /* phrase: + the survivor queue and the survivors' positions staged for the predicates, u16 [T][kPosFast][64 lanes] (xgm_posfilter.h).
  * Inside xgm_andw_kernel the wave's slice (andw_wave_bytes) is larger than this for any tab_terms >= T. */
 __host__ __device__ constexpr size_t dense_wave_bytes(bool phrase, uint32_t terms = kDenseT) {
-    return (size_t)kDenseCap * 8 + (size_t)kDenseCap * 4 + (size_t)kDenseT * kDenseSpg * 4 + (size_t)kDenseRing * 4 +
-           (phrase ? (size_t)kDenseSq * 16 + (size_t)terms * kPosFast * 64 * 2 : 0);
+    return kDenseCoreBytes + (phrase ? (size_t)kDenseSq * 16 + (size_t)terms * kPosFast * 64 * 2 : kDenseP2Bytes);
 }
 
 typedef uint32_t dense_u4 __attribute__((ext_vector_type(4)));
@@ -232,10 +236,15 @@ __device__ __forceinline__ void xgm_dense_unit(const xgm_seg_dev& seg, const xgm
     uint32_t* tk_d = reinterpret_cast<uint32_t*>(base + (size_t)kDenseCap * 8);
     uint32_t* rs = reinterpret_cast<uint32_t*>(base + (size_t)kDenseCap * 12);
     uint32_t* ring = reinterpret_cast<uint32_t*>(base + (size_t)kDenseCap * 12 + (size_t)kDenseT * kDenseSpg * 4);
-    uint64_t* sq_w = reinterpret_cast<uint64_t*>(base + dense_wave_bytes(false));           /* PHRASE only: the survivor queue */
-    uint32_t* sq_d = reinterpret_cast<uint32_t*>(base + dense_wave_bytes(false) + (size_t)kDenseSq * 8);
+    uint64_t* sq_w = reinterpret_cast<uint64_t*>(base + kDenseCoreBytes);                   /* PHRASE only: the survivor queue */
+    uint32_t* sq_d = reinterpret_cast<uint32_t*>(base + kDenseCoreBytes + (size_t)kDenseSq * 8);
     uint32_t* sq_v = sq_d + kDenseSq;
     uint16_t* lpos = reinterpret_cast<uint16_t*>(sq_v + kDenseSq);                          /* PHRASE only: the survivors' positions, [T][kPosFast][64] */
+    /* plain only: the containers' wdf != 1 summaries, [kDenseSpg][low / high half][kDenseT].  A candidate is a member of every term (the AND of the bitmaps says
+     * so): where the summary bit of its slot is clear its wdf is 1 and the byte is not fetched (issue).  No summary (wave-uniform): every byte is. */
+    uint32_t* p2s = reinterpret_cast<uint32_t*>(base + kDenseCoreBytes);
+    bool use_p2 = false;
+    if constexpr (!PHRASE) use_p2 = seg.dense_p2 != nullptr;
 
     const uint32_t s_begin = wk.s_begin, s_end = wk.s_end;
     const bool empty = (q.flags & XGM_QF_EMPTY) || s_begin >= s_end || k == 0;
@@ -256,14 +265,17 @@ __device__ __forceinline__ void xgm_dense_unit(const xgm_seg_dev& seg, const xgm
     for (uint32_t i = 0; i < kDenseT * kDenseSpg; i += 64u) {
         const uint32_t e = i + lane, t = e / kDenseSpg, x = e % kDenseSpg;
         uint32_t off = 0;
+        unsigned long long p2w = 0;
         if (t < T && x < n_local) {
             const uint32_t id = q.term_id[t];
             const uint32_t dn = id != 0xFFFFFFFFu ? seg.dense_id[id] : 0xFFFFFFFFu;
             if (dn != 0xFFFFFFFFu) off = seg.dense_dir[(size_t)dn * seg.n_stripes + (s_begin + x)];
+            if constexpr (!PHRASE) { if (use_p2 && dn != 0xFFFFFFFFu) p2w = seg.dense_p2[(size_t)dn * seg.n_stripes + (s_begin + x)]; }
         }
         rs[x * kDenseT + t] = off;                                 /* stripe-major: a candidate's four offsets are ONE 16-byte LDS read (issue) */
+        if constexpr (!PHRASE) { if (use_p2) { p2s[x * (2u * kDenseT) + t] = (uint32_t)p2w; p2s[x * (2u * kDenseT) + kDenseT + t] = (uint32_t)(p2w >> 32); } }
     }
-    if (TALLY) { cn_aux += T * n_local; }
+    if (TALLY) { cn_aux += T * n_local * (use_p2 ? 3u : 1u); }
     wave_lds_fence();
 
     /* PHRASE: the units of a query share what they learn (see xgm_andw_kernel): a 256-bucket histogram of the weights of the
@@ -645,10 +657,28 @@ __device__ __forceinline__ void xgm_dense_unit(const xgm_seg_dev& seg, const xgm
         uint32_t wv[kDenseT];
         const dense_u4 ro4 = *reinterpret_cast<const dense_u4*>(&rs[x * kDenseT]);
         const uint32_t ro[kDenseT] = {ro4.x, ro4.y, ro4.z, ro4.w};
+        /* plain: which bytes have to be fetched — the summary bit of the candidate's slot, per term (the half of the words that holds it: one 16-byte
+         * LDS read); without a summary every lane asks, the idle ones included, as ever */
+        uint32_t ask[kDenseT] = {1u, 1u, 1u, 1u};
+        if constexpr (!PHRASE) {
+            if (use_p2) {
+                const uint32_t j = slot >> (SB - 6u);
+                const dense_u4 pw = *reinterpret_cast<const dense_u4*>(&p2s[x * (2u * kDenseT) + (j >> 5) * kDenseT]);
+                const uint32_t live = valid ? 1u : 0u;
+                ask[0] = (pw.x >> (j & 31u)) & live; ask[1] = (pw.y >> (j & 31u)) & live; ask[2] = (pw.z >> (j & 31u)) & live; ask[3] = (pw.w >> (j & 31u)) & live;
+            }
+        }
 #pragma unroll
         for (uint32_t t = 0; t < kDenseT; ++t) {
             wv[t] = 1u;                                            /* (T is wave-uniform: a scalar branch, the gathers still go out back to back) */
-            if (t < kDenseGatherAll || t < T) wv[t] = seg.dense_data[(size_t)ro[t < T ? t : T - 1u] * 16 + (size_t)NW * 4 + slot];
+            if (t < kDenseGatherAll || t < T) {
+                if constexpr (PHRASE) {
+                    wv[t] = seg.dense_data[(size_t)ro[t < T ? t : T - 1u] * 16 + (size_t)NW * 4 + slot];
+                } else {
+                    wv[t] = 2u;                                    /* wdf 1: what the byte would read */
+                    if (ask[t]) wv[t] = seg.dense_data[(size_t)ro[t < T ? t : T - 1u] * 16 + (size_t)NW * 4 + slot];
+                }
+            }
         }
         /* the document's length: from the narrow copy when the shard has one (64 / 32 documents per memory sector instead of 16) */
         /* (what the load returns is parked as it is — the narrow copy's base is added by weigh(): an addition here made the compiler wait
@@ -658,8 +688,21 @@ __device__ __forceinline__ void xgm_dense_unit(const xgm_seg_dev& seg, const xgm
         else if (dl_bits == 16u) dlen = (uint32_t)reinterpret_cast<const uint16_t*>(seg.doclen_narrow)[did];
         else dlen = seg.doclen[did];
         if (TALLY) {
-            const uint32_t sec = tally_sectors(valid, did, 6u);
-            cn_probe += T * sec; cn_probe_raw += T * n;
+            if (use_p2) {
+                /* the lanes that ask, and the distinct sectors among them (docids ascending: one per first asking lane that falls into it) */
+#pragma unroll
+                for (uint32_t t = 0; t < kDenseT; ++t) {
+                    if (t < T) {
+                        const uint64_t am = __ballot(ask[t] != 0u), below = am & ((1ull << lane) - 1ull);
+                        const uint32_t prev = (uint32_t)__shfl((int)did, below ? 63 - (int)__builtin_clzll(below) : (int)lane);
+                        cn_probe += (uint32_t)__popcll(__ballot(ask[t] != 0u && (below == 0ull || (prev >> 6) != (did >> 6))));
+                        cn_probe_raw += (uint32_t)__popcll(am);
+                    }
+                }
+            } else {
+                const uint32_t sec = tally_sectors(valid, did, 6u);
+                cn_probe += T * sec; cn_probe_raw += T * n;
+            }
             cn_dl += tally_sectors(valid, did, dl_bits == 8u ? 6u : dl_bits == 16u ? 5u : 4u); cn_dl_raw += n;
         }
         const uint32_t c_b = XGM_CLK();

@@ -26,8 +26,9 @@
 constexpr uint32_t kFlatSq = 128;          /* positional survivors waiting for their test */
 
 /* bytes of the wave's LDS slice a unit uses (the slice of xgm_andw_kernel is larger for any tab_terms >= terms: checked by plan_batch) */
+constexpr size_t kFlatCoreBytes = (size_t)kDenseCap * 12 + (size_t)kDenseT * kDenseSpg * 4;      /* top-k buffer + container offsets */
 __host__ __device__ constexpr size_t flat_wave_bytes(bool phrase, uint32_t terms) {
-    return (size_t)kDenseCap * 12 + (size_t)kDenseT * kDenseSpg * 4 + (phrase ? (size_t)kFlatSq * (16 + 4 * kDenseT) + (size_t)terms * kPosFast * 64 * 2 : 0);
+    return kFlatCoreBytes + (phrase ? (size_t)kFlatSq * (16 + 4 * kDenseT) + (size_t)terms * kPosFast * 64 * 2 : kDenseP2Bytes);
 }
 
 template <bool PHRASE, bool TALLY, bool LIST = false, bool ALL = false>
@@ -69,11 +70,15 @@ __device__ __forceinline__ void xgm_flat_unit(const xgm_seg_dev& seg, const xgm_
     uint32_t* tk_d = reinterpret_cast<uint32_t*>(base + (size_t)kDenseCap * 8);
     uint32_t* rs = reinterpret_cast<uint32_t*>(base + (size_t)kDenseCap * 12);              /* [kDenseT][kDenseSpg] container offsets of the dense terms */
     /* PHRASE: the survivor queue (weight bits, docid, wdf + 1 bytes, position starts of the flat terms) and the staged positions */
-    uint64_t* sq_w = reinterpret_cast<uint64_t*>(base + flat_wave_bytes(false, 0));
+    uint64_t* sq_w = reinterpret_cast<uint64_t*>(base + kFlatCoreBytes);
     uint32_t* sq_d = reinterpret_cast<uint32_t*>(sq_w + kFlatSq);
     uint32_t* sq_v = sq_d + kFlatSq;
     uint32_t* sq_p = sq_v + kFlatSq;                                                        /* [kDenseT][kFlatSq] */
     uint16_t* lpos = reinterpret_cast<uint16_t*>(sq_p + (size_t)kDenseT * kFlatSq);
+    /* plain only: the wdf != 1 summaries of the container terms, [kDenseT][kDenseSpg] like rs (xgm_seg_dev::dense_p2; NULL, wave-uniform: none) */
+    uint64_t* p2s = reinterpret_cast<uint64_t*>(base + kFlatCoreBytes);
+    bool use_p2 = false;
+    if constexpr (!PHRASE) use_p2 = seg.dense_p2 != nullptr;
 
     const uint32_t s_begin = wk.s_begin, s_end = wk.s_end;
     const bool empty = (q.flags & XGM_QF_EMPTY) || s_begin >= s_end || k == 0;
@@ -112,16 +117,24 @@ __device__ __forceinline__ void xgm_flat_unit(const xgm_seg_dev& seg, const xgm_
     for (uint32_t i = 0; i < kDenseT * kDenseSpg; i += 64u) {
         const uint32_t e = i + lane, t = e / kDenseSpg, x = e % kDenseSpg;
         uint32_t off = 0;
+        unsigned long long p2w = 0;
         if (t < T && x < n_local) {
             uint32_t d = 0xFFFFFFFFu;
 #pragma unroll
             for (uint32_t u = 0; u < kDenseT; ++u) if (u == t) d = dn[u];
             if (d != 0xFFFFFFFFu) off = seg.dense_dir[(size_t)d * seg.n_stripes + (s_begin + x)];
+            if constexpr (!PHRASE) { if (use_p2 && d != 0xFFFFFFFFu) p2w = seg.dense_p2[(size_t)d * seg.n_stripes + (s_begin + x)]; }
         }
         rs[e] = off;
+        if constexpr (!PHRASE) { if (use_p2) p2s[e] = p2w; }
     }
-    if (TALLY) { cn_aux += T * n_local; }
+    if (TALLY) { cn_aux += T * n_local * (use_p2 ? 3u : 1u); }
     wave_lds_fence();
+    /* plain conjunctions of three or four terms whose screen has containers: stage A asks the screen's BITMAP for membership — a sector of 512
+     * documents where the wdf byte's holds 64, and a lead term leaves several postings per 512 — and the survivors fetch the screen's wdf byte in
+     * stage B next to the remaining terms' (or take wdf 1 from the summary).  xgm_seg_dev::bit_screen: A/B switch */
+    bool bit_screen = false;
+    if constexpr (!PHRASE) bit_screen = T > 2u && dn[1] != 0xFFFFFFFFu && rfl32(seg.bit_screen) != 0u;
 
     uint32_t tkn = 0;                                              /* wave-uniform top-k state */
     bool theta_valid = false;
@@ -377,10 +390,43 @@ __device__ __forceinline__ void xgm_flat_unit(const xgm_seg_dev& seg, const xgm_
         bool present = valid, alive = valid, none = false;
 #pragma unroll
         for (uint32_t t = 1; t < kDenseT; ++t) {
-            if (t == 2u && T > 2u) { alive = present; none = __ballot(present) == 0ull; }
+            if (t == 2u && T > 2u) {
+                alive = present; none = __ballot(present) == 0ull;
+                if constexpr (!PHRASE) {
+                    if (bit_screen && !none) {
+                        /* the screen's wdf for its survivors (members: their stripe has a container); 1 where the summary bit is clear */
+                        bool ask = alive;
+                        if (use_p2) {
+                            const uint32_t j = slot >> (SB - 6u);
+                            ask = alive && ((reinterpret_cast<const uint32_t*>(p2s)[(kDenseSpg + x) * 2u + (j >> 5)] >> (j & 31u)) & 1u) != 0u;
+                        }
+                        wv[1] = alive ? 2u : 0u;
+                        if (ask) wv[1] = (uint32_t)seg.dense_data[(size_t)rs[kDenseSpg + x] * 16 + (size_t)NW * 4 + slot];
+                        if (TALLY) {
+                            const uint64_t am = __ballot(ask), below = am & ((1ull << lane) - 1ull);
+                            const uint32_t prev = (uint32_t)__shfl((int)did, below ? 63 - (int)__builtin_clzll(below) : (int)lane);
+                            cn_probe += (uint32_t)__popcll(__ballot(ask && (below == 0ull || (prev >> 6) != (did >> 6))));
+                            cn_probe_raw += (uint32_t)__popcll(am);
+                        }
+                    }
+                }
+            }
             if (t < T && !none) {
                 wv[t] = 0u;
-                if (dn[t] != 0xFFFFFFFFu) {
+                if (!PHRASE && t == 1u && bit_screen) {
+                    /* one bit of the bitmap of the container of the candidate's own stripe: a member's wdf + 1 comes with stage B */
+                    const uint32_t off = rs[kDenseSpg + x];
+                    const bool ask = alive && off != 0u;
+                    uint32_t bw = 0u;
+                    if (ask) bw = reinterpret_cast<const uint32_t*>(seg.dense_data + (size_t)off * 16)[slot >> 5];
+                    wv[t] = (bw >> (slot & 31u)) & 1u;             /* (a placeholder, replaced at stage B) */
+                    if (TALLY) {
+                        const uint64_t am = __ballot(ask), below = am & ((1ull << lane) - 1ull);
+                        const uint32_t prev = (uint32_t)__shfl((int)did, below ? 63 - (int)__builtin_clzll(below) : (int)lane);
+                        cn_probe += (uint32_t)__popcll(__ballot(ask && (below == 0ull || (prev >> 9) != (did >> 9))));
+                        cn_probe_raw += (uint32_t)__popcll(am);
+                    }
+                } else if (dn[t] != 0xFFFFFFFFu) {
                     /* one byte of the container of the candidate's own stripe */
                     const uint32_t off = rs[t * kDenseSpg + x];
                     const bool ask = alive && off != 0u;

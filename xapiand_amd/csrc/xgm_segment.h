@@ -117,6 +117,12 @@ typedef struct {
     const uint32_t* flat_did;
     const unsigned char* flat_wdf;
     const uint32_t* flat_pos;       /* indexes with positions: position-entry offset (relative to the term's list) of every flat posting's first position, or NULL */
+    /* A 64-bit summary of every container's wdf bytes (built with the containers): bit j of dense_p2[dense * n_stripes + stripe] is set iff a posting in
+     * slots [j W/64, (j + 1) W/64) has a wdf other than 1 — bits2 says wdf >= 2, but a boolean term's postings carry wdf 0 and their byte reads 1, not 2;
+     * 0 where there is no container.  Beyond the most frequent terms almost every wdf is 1: a conjunction that knows a document is a member (the AND
+     * of the bitmaps, a bit screen) and finds the bit clear has its wdf without a probe.  NULL: none. */
+    const unsigned long long* dense_p2;
+    uint32_t bit_screen;            /* xgm_flat_unit asks the screen term's bitmap (a sector of 512 documents) for membership instead of its wdf bytes (64) */
 } xgm_seg_dev;
 
 #define XGM_DENSE_MIN_AVG 32u          /* postings per stripe (on average) that make a term dense     */
