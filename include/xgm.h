@@ -168,6 +168,28 @@ int xgm_segment_refresh_from_glass(const char* old_segment_path, const char* gla
  * Replaces: Document::get_value per candidate in the matcher (matcher/matcher.cc:509-517). */
 int xgm_glass_export_column(const char* glass_dir, uint32_t slot, const char* out_path);
 
+/* The same slot as a LIST column file: Xapiand stores every field's slot value as a StringList (reference src/serialise_list.h:301-356) —
+ * a single value raw, several as '\0' followed by (length, bytes) pairs — and its `_range` over such a slot walks the list
+ * (multivalue/range.cc).  Each value is split exactly as StringList::unserialise does (xgm_debug_split_string_list below) and the ELEMENTS
+ * are ranked:
+ *   "XGMLST1\0", u32 slot, u32 lastdocid, u32 n_distinct, u32 0, u64 n_elem,
+ *   u32 off[lastdocid + 2]         the elements of document d are elem[off[d] .. off[d + 1]); off[0] = off[1] = 0 (docid 0 does not exist)
+ *   u32 elem[n_elem]               1 + the bytewise rank of the element among the slot's distinct elements, in STORED order, duplicates kept
+ *   u64 voff[n_distinct + 1], bytes the distinct elements, ascending (the tail of an XGMCOL1 file)
+ * Walks the value chunks xgm_glass_export_column walks.  A length that runs past its value fails the export with XGM_E_INVALID (the
+ * reference throws SerialisationError there).  The value "\0" alone gives a document of ZERO elements: the reference's front() on such a
+ * list is undefined, here such a document never passes a clause.
+ * Replaces: StringList(get_value()) per candidate document in MultipleValueRange / GE / LE::insideRange(). */
+int xgm_glass_export_list_column(const char* glass_dir, uint32_t slot, const char* out_path);
+
+/* The splitter of xgm_glass_export_list_column on one slot value, for tests: StringList::unserialise (serialise_list.h:333-348) with
+ * unserialise_length_and_check (reference src/length.cc:64-96).  An empty value has no elements; a first byte other than '\0' makes the
+ * whole value the one element; otherwise (length, bytes) pairs follow the '\0' — a length below 255 is one byte, 0xff introduces 7-bit
+ * groups, least significant first, the last one with bit 7 SET, plus 255.  Returns the number of elements and writes the first
+ * min(count, cap) as offsets into value (elem_begin) and lengths (elem_len; both may be NULL when cap is 0), or XGM_E_INVALID for a
+ * truncated length or a length greater than what is left of the value. */
+int64_t xgm_debug_split_string_list(const char* value, size_t len, uint32_t* elem_begin, uint32_t* elem_len, uint32_t cap);
+
 /* The committed revision and statistics of a glass shard, from its version file alone (what
  * Database::get_revision / get_doccount / get_lastdocid / get_total_length would answer): the key under
  * which an exported segment is cached, cheap enough to poll.  Any output pointer may be NULL. */
@@ -426,6 +448,20 @@ int xgm_index_attach_column(xgm_index* idx, const char* column_path);
  * sorts: reference src/database/handler.cc:1269); any slot number may be used for such a synthetic column. */
 int xgm_index_attach_column_ordinals(xgm_index* idx, uint32_t slot, const uint32_t* ord, uint32_t n_ord, uint32_t n_distinct);
 
+/* Load a LIST column file (xgm_glass_export_list_column) into HBM next to the index, for XGM_RANGE_LIST* clauses of xgm_filter_build.  List
+ * columns live in a map of their own: the same slot may also have its plain whole-value column attached (sorts, spies and collapse keep
+ * reading that one), neither replaces the other; attaching a slot's list column again replaces the earlier list column.  On the device a
+ * document costs 4 bytes (head[d]: 0 = no element, an ordinal = its one element, bit 31 set = an index into ext), and only a document of
+ * two or more elements adds 4 bytes per element + 4 to ext, the documents' lists in ascending docid order.  XGM_E_INVALID for another
+ * lastdocid or a malformed file; XGM_UNSUPPORTED for more than 0x7FFFFFFF distinct elements or an ext of 2^31 words or more.
+ * Replaces: the slot's value stream read and unserialised per query by MultipleValueRange / GE / LE (multivalue/range.cc). */
+int xgm_index_attach_list_column(xgm_index* idx, const char* list_column_path);
+/* The same from memory, in CSR form: the elements of document d are elem[off[d] .. off[d + 1]), each 1 + the rank of the element among
+ * n_distinct distinct elements, in stored order.  n_off must be lastdocid + 2, off monotone with off[0] = off[1] = 0 (docid 0 does not
+ * exist) and off[n_off - 1] = n_elem, every element in 1 .. n_distinct: XGM_E_INVALID otherwise.  elem may be NULL when n_elem is 0. */
+int xgm_index_attach_list_column_ordinals(xgm_index* idx, uint32_t slot, const uint32_t* off, uint32_t n_off, const uint32_t* elem, uint64_t n_elem,
+                                          uint32_t n_distinct);
+
 #define XGM_SORT_VALUE 1u                 /* Enquire::set_sort_by_value                  (msetcmp.cc:64-73)   */
 #define XGM_SORT_VALUE_RELEVANCE 2u       /* Enquire::set_sort_by_value_then_relevance   (msetcmp.cc:75-86)   */
 #define XGM_SORT_RELEVANCE_VALUE 3u       /* Enquire::set_sort_by_relevance_then_value   (msetcmp.cc:88-101)  */
@@ -498,10 +534,24 @@ int xgm_search_collapsed_batch(xgm_index* idx, const xgm_query* qs, uint32_t nq,
  * Replaces: ValueRangePostList / ValueGePostList under OP_FILTER as the optimiser builds them (api/queryinternal.cc:1146-1271). */
 #define XGM_MAX_RANGES 4
 #define XGM_ORD_MAX 0xFFFFFFFFu
+/* What a clause tests.  XGM_RANGE_VALUE: the document's ONE ordinal in a plain column (xgm_index_attach_column*), as above.  The three
+ * list kinds test the document's LIST of element ordinals in a list column (xgm_index_attach_list_column*) by Xapiand's `_range` over a
+ * multi-valued slot — MultipleValueRange / MultipleValueGE / MultipleValueLE::insideRange() (reference src/multivalue/range.cc:352-368,
+ * 484-494, 609-619), with `e >= start` as e >= lo_ord and `e <= end` as e <= hi_ord, in the list's STORED order:
+ *   XGM_RANGE_LIST     no element: no; hi_ord < the first element: no; lo_ord > the last element: no; else the first element in stored
+ *                      order with e >= lo_ord decides — the document passes iff that e <= hi_ord (no such element: no)
+ *   XGM_RANGE_LIST_GE  has an element and the last one >= lo_ord (hi_ord ignored)
+ *   XGM_RANGE_LIST_LE  has an element and the first one <= hi_ord (lo_ord ignored; it must still be >= 1)
+ * On the ascending, duplicate-free lists Xapiand writes, LIST is "some element lies in [lo_ord, hi_ord]"; on any other list the device
+ * answers as the reference does, not by that paraphrase. */
+#define XGM_RANGE_VALUE 0u
+#define XGM_RANGE_LIST 1u
+#define XGM_RANGE_LIST_GE 2u
+#define XGM_RANGE_LIST_LE 3u
 typedef struct {
-    uint32_t slot;                        /* value slot of an attached column                                  */
+    uint32_t slot;                        /* value slot of an attached column (kind 0) or list column (kinds 1 .. 3) */
     uint32_t lo_ord, hi_ord;              /* lo_ord <= ordinal <= hi_ord; lo_ord >= 1, hi_ord may be XGM_ORD_MAX, lo_ord > hi_ord: nothing passes */
-    uint32_t reserved;
+    uint32_t kind;                        /* XGM_RANGE_*; 0 = XGM_RANGE_VALUE                                  */
 } xgm_value_range;
 typedef struct xgm_filter xgm_filter;     /* opaque, immutable once built */
 
@@ -510,7 +560,9 @@ typedef struct xgm_filter xgm_filter;     /* opaque, immutable once built */
  * value >= begin (1 for an empty begin), *hi_ord = the number of values <= end, or XGM_ORD_MAX with XGM_RANGE_NO_END (end is then
  * ignored).  begin > end gives lo_ord > hi_ord.  Host only: no device needed, works beside an index opened with XGM_DEVICE_NONE.  A caller
  * that attached ordinals from memory (xgm_index_attach_column_ordinals) computes the interval from its own values.
- * Replaces: the string comparisons of ValueRangePostList::next / skip_to per candidate document. */
+ * column_path may also be a list column file (xgm_glass_export_list_column): the search is then over its distinct ELEMENTS, and the
+ * interval is one of element ordinals — what a XGM_RANGE_LIST* clause takes.
+ * Replaces: the string comparisons of ValueRangePostList::next / skip_to (and of MultipleValue*::insideRange) per candidate document. */
 #define XGM_RANGE_NO_END 1u
 int xgm_column_ord_range(const char* column_path, const char* begin, size_t begin_len, const char* end, size_t end_len, uint32_t flags,
                          uint32_t* lo_ord, uint32_t* hi_ord);
@@ -521,7 +573,12 @@ int xgm_column_ord_range(const char* column_path, const char* begin, size_t begi
  * passing.  XGM_UNSUPPORTED when a slot has no column attached; XGM_E_INVALID for n_ranges 0 or above XGM_MAX_RANGES or a lo_ord of 0;
  * XGM_E_NO_DEVICE on an index without a device.  The filter belongs to the index's lastdocid (and to the columns as they were when it
  * was built): another revision needs another filter.
- * Replaces: one ValueRangePostList per clause walking the slot's value stream (matcher/valuerangepostlist.cc). */
+ * Clauses of all four kinds may be mixed.  A list kind needs the slot's LIST column (XGM_UNSUPPORTED without one, whether or not the slot's
+ * plain column is attached), a kind above XGM_RANGE_LIST_LE is XGM_E_INVALID.  A filter of XGM_RANGE_VALUE clauses alone runs the kernel it
+ * always ran; any list clause selects a second one, which reads 4 bytes of head per document and clause and, only for documents of two or
+ * more elements, their lists.
+ * Replaces: one ValueRangePostList per clause walking the slot's value stream (matcher/valuerangepostlist.cc); for the list kinds one
+ * MultipleValueRange / MultipleValueGE / MultipleValueLE posting source unserialising a StringList per document (multivalue/range.cc). */
 int xgm_filter_build(xgm_index*, const xgm_value_range* ranges, uint32_t n_ranges, xgm_filter** out, uint64_t* n_docs);
 /* The bitmap on the host: bit d & 31 of words[d >> 5] is set when document d passes; n_words = ceil((lastdocid + 1) / 32).  Bit 0 of word 0
  * (docid 0) and the bits beyond lastdocid are clear.  For tests, and for a hook that wants to see where n_docs came from. */

@@ -95,9 +95,10 @@ XGM_SORT_VALUE, XGM_SORT_VALUE_RELEVANCE, XGM_SORT_RELEVANCE_VALUE = 1, 2, 3
 
 
 class ValueRange(C.Structure):
-    _fields_ = [("slot", C.c_uint32), ("lo_ord", C.c_uint32), ("hi_ord", C.c_uint32), ("reserved", C.c_uint32)]
+    _fields_ = [("slot", C.c_uint32), ("lo_ord", C.c_uint32), ("hi_ord", C.c_uint32), ("kind", C.c_uint32)]
 
 
+XGM_RANGE_VALUE, XGM_RANGE_LIST, XGM_RANGE_LIST_GE, XGM_RANGE_LIST_LE = 0, 1, 2, 3
 XGM_MAX_RANGES = 4
 XGM_ORD_MAX = 0xFFFFFFFF
 XGM_RANGE_NO_END = 1
@@ -122,6 +123,10 @@ _API = [
     ("xgm_segment_build_from_glass", C.c_int, [C.c_char_p, C.c_uint32, C.c_char_p]),
     ("xgm_glass_export_column", C.c_int, [C.c_char_p, C.c_uint32, C.c_char_p]),
     ("xgm_index_attach_column", C.c_int, [C.c_void_p, C.c_char_p]),
+    ("xgm_glass_export_list_column", C.c_int, [C.c_char_p, C.c_uint32, C.c_char_p]),
+    ("xgm_debug_split_string_list", C.c_int64, [C.c_char_p, C.c_size_t, _P(C.c_uint32), _P(C.c_uint32), C.c_uint32]),
+    ("xgm_index_attach_list_column", C.c_int, [C.c_void_p, C.c_char_p]),
+    ("xgm_index_attach_list_column_ordinals", C.c_int, [C.c_void_p, C.c_uint32, _P(C.c_uint32), C.c_uint32, _P(C.c_uint32), C.c_uint64, C.c_uint32]),
     ("xgm_search_sorted", C.c_int, [C.c_void_p, _P(Query), _P(SortSpec), _P(Hit), _P(C.c_uint32), _P(ResultHdr)]),
     ("xgm_search_sorted_batch", C.c_int, [C.c_void_p, _P(Query), C.c_uint32, _P(SortSpec), C.c_uint32, _P(Hit), _P(C.c_uint32), _P(ResultHdr)]),
     ("xgm_search_sorted_spy_batch", C.c_int, [C.c_void_p, _P(Query), C.c_uint32, _P(SortSpec), C.c_uint32, _P(Hit), _P(C.c_uint32), _P(ResultHdr),

@@ -293,6 +293,7 @@ extern "C" void xgm_index_close(xgm_index* idx) {
     if (idx->d_dense_p2) hipFree(idx->d_dense_p2);
     if (idx->d_dense_data) hipFree(idx->d_dense_data);
     for (auto& c : idx->columns) if (c.second.first) hipFree(c.second.first);
+    for (auto& c : idx->list_columns) { if (c.second.head) hipFree(c.second.head); if (c.second.ext) hipFree(c.second.ext); }
     for (void* c : idx->retired_columns) hipFree(c);
     delete idx;
 }
@@ -1653,6 +1654,76 @@ extern "C" int xgm_index_attach_column_ordinals(xgm_index* idx, uint32_t slot, c
     return attach_ordinals(idx, slot, ord, n_ord, n_distinct);
 }
 
+/* ---- list columns (include/xgm.h: xgm_index_attach_list_column): a slot's StringList per document, for XGM_RANGE_LIST* clauses ------
+ * The CSR (off, elem) becomes head[lastdocid + 1] — 0, the one element's ordinal, or 0x80000000 | i — and ext[]: per document of two
+ * or more elements, in ascending docid order, n followed by its n ordinals in stored order (xgm_filter_mark_lists_kernel, xgm_filter.h).
+ * A single-valued document then costs the filter what it costs in a plain column. */
+static int attach_list(xgm_index* idx, uint32_t slot, const uint32_t* off, size_t n_off, const uint32_t* elem, uint64_t n_elem, uint32_t n_distinct) {
+    if (n_off != (size_t)idx->hdr.lastdocid + 2u) return xgm_set_error(XGM_E_INVALID, "list column of %zu offsets, index of %u documents (another revision?)", n_off, idx->hdr.lastdocid);
+    if (off[0] != 0u || off[1] != 0u) return xgm_set_error(XGM_E_INVALID, "list column: elements for docid 0");
+    for (size_t d = 0; d + 1 < n_off; ++d) if (off[d] > off[d + 1]) return xgm_set_error(XGM_E_INVALID, "list column: offsets decrease at document %zu", d);
+    if (off[n_off - 1] != n_elem) return xgm_set_error(XGM_E_INVALID, "list column: the last offset is %u, %llu elements", off[n_off - 1], (unsigned long long)n_elem);
+    if (n_distinct > 0x7FFFFFFFu) return XGM_UNSUPPORTED;                /* bit 31 of a head says "a list" */
+    for (uint64_t i = 0; i < n_elem; ++i)
+        if (elem[i] == 0u || elem[i] > n_distinct) return xgm_set_error(XGM_E_INVALID, "list column: element ordinal %u outside 1 .. %u", elem[i], n_distinct);
+    std::vector<uint32_t> head(n_off - 1, 0u), ext;
+    for (size_t d = 1; d + 1 < n_off; ++d) {
+        const uint32_t n = off[d + 1] - off[d];
+        if (n == 1u) head[d] = elem[off[d]];
+        else if (n >= 2u) {
+            if (ext.size() + (size_t)n + 1u >= ((size_t)1 << 31)) return XGM_UNSUPPORTED;
+            head[d] = 0x80000000u | (uint32_t)ext.size();
+            ext.push_back(n);
+            ext.insert(ext.end(), elem + off[d], elem + off[d + 1]);
+        }
+    }
+    int rc = use_device(idx->device);
+    if (rc) return rc;
+    void* d_head = nullptr;
+    void* d_ext = nullptr;
+    HIP_TRY(hipMalloc(&d_head, head.size() * 4));
+    hipError_t e = hipMemcpy(d_head, head.data(), head.size() * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess && !ext.empty()) {
+        e = hipMalloc(&d_ext, ext.size() * 4);
+        if (e == hipSuccess) e = hipMemcpy(d_ext, ext.data(), ext.size() * 4, hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess) { hipFree(d_head); if (d_ext) hipFree(d_ext); return xgm_launch_error("list column upload", (int)e, hipGetErrorString(e)); }
+    std::lock_guard<std::mutex> lk(idx->columns_mu);
+    xgm_index::ListColumn& col = idx->list_columns[slot];
+    if (col.head) idx->retired_columns.push_back(col.head);
+    if (col.ext) idx->retired_columns.push_back(col.ext);
+    col.head = d_head; col.ext = d_ext; col.n_distinct = n_distinct;
+    return XGM_OK;
+}
+
+extern "C" int xgm_index_attach_list_column_ordinals(xgm_index* idx, uint32_t slot, const uint32_t* off, uint32_t n_off, const uint32_t* elem, uint64_t n_elem,
+                                                     uint32_t n_distinct) {
+    if (!idx || !off || (n_elem && !elem)) return xgm_set_error(XGM_E_INVALID, "null argument");
+    if (idx->device == XGM_DEVICE_NONE) return xgm_set_error(XGM_E_NO_DEVICE, "index opened without a device");
+    if (n_off < 2u) return xgm_set_error(XGM_E_INVALID, "list column of %u offsets", n_off);
+    return attach_list(idx, slot, off, n_off, elem, n_elem, n_distinct);
+}
+
+extern "C" int xgm_index_attach_list_column(xgm_index* idx, const char* path) {
+    if (!idx || !path) return xgm_set_error(XGM_E_INVALID, "null argument");
+    if (idx->device == XGM_DEVICE_NONE) return xgm_set_error(XGM_E_NO_DEVICE, "index opened without a device");
+    FILE* f = fopen(path, "rb");
+    if (!f) return xgm_set_error(XGM_E_IO, "cannot open %s: %s", path, strerror(errno));
+    char magic[8];
+    uint32_t h32[4];
+    uint64_t n_elem = 0;
+    std::vector<uint32_t> off, elem;
+    bool ok = fread(magic, 1, 8, f) == 8 && fread(h32, 4, 4, f) == 4 && fread(&n_elem, 8, 1, f) == 1 && memcmp(magic, "XGMLST1", 8) == 0;
+    if (ok && h32[1] != idx->hdr.lastdocid) { fclose(f); return xgm_set_error(XGM_E_INVALID, "%s: list column of %u documents, index of %u (another revision?)", path, h32[1], idx->hdr.lastdocid); }
+    ok = ok && n_elem <= 0xFFFFFFFFull;
+    if (ok) { off.resize((size_t)h32[1] + 2); ok = fread(off.data(), 4, off.size(), f) == off.size(); }
+    ok = ok && off.back() == n_elem;                                     /* (before the elements are sized by it) */
+    if (ok) { elem.resize((size_t)n_elem); ok = fread(elem.data(), 4, elem.size(), f) == elem.size(); }
+    fclose(f);
+    if (!ok) return xgm_set_error(XGM_E_INVALID, "%s is not a list column file", path);
+    return attach_list(idx, h32[0], off.data(), off.size(), elem.data(), n_elem, h32[2]);
+}
+
 /* a scratch goes back to the pool only when nothing enqueued on its stream still uses it (the early returns) */
 /* The whole-match list of a replay / xgm_search_all (d_all) is sized by the match's upper bound — hundreds of MB for a frequent-term query on a
  * 10 M-document shard — and the pool keeps a scratch per concurrent caller: ONE scratch of the pool keeps such a list (a caller that replays one
@@ -2051,7 +2122,13 @@ extern "C" int xgm_column_ord_range(const char* column_path, const char* begin, 
     uint32_t h32[4];
     std::vector<uint64_t> off;
     std::vector<char> bytes;
-    bool ok = fread(magic, 1, 8, f) == 8 && fread(h32, 4, 4, f) == 4 && memcmp(magic, "XGMCOL1", 8) == 0;
+    bool ok = fread(magic, 1, 8, f) == 8 && fread(h32, 4, 4, f) == 4;
+    const bool list = ok && memcmp(magic, "XGMLST1", 8) == 0;                          /* a list column: the same tail, of distinct ELEMENTS */
+    ok = ok && (list || memcmp(magic, "XGMCOL1", 8) == 0);
+    if (list) {
+        uint64_t n_elem = 0;
+        ok = fread(&n_elem, 8, 1, f) == 1 && n_elem <= 0xFFFFFFFFull && fseek(f, (long)(((size_t)h32[1] + 2 + (size_t)n_elem) * 4), SEEK_CUR) == 0;   /* (off, elem) */
+    } else
     ok = ok && fseek(f, (long)(((size_t)h32[1] + 1) * 4), SEEK_CUR) == 0;              /* (the ordinals) */
     if (ok) { off.resize((size_t)h32[2] + 1); ok = fread(off.data(), 8, off.size(), f) == off.size(); }
     for (size_t i = 0; ok && i + 1 < off.size(); ++i) ok = off[i] <= off[i + 1];
@@ -2082,13 +2159,23 @@ extern "C" int xgm_filter_build(xgm_index* idx, const xgm_value_range* ranges, u
     if (n_ranges == 0 || n_ranges > XGM_MAX_RANGES) return xgm_set_error(XGM_E_INVALID, "%u range clauses (1 .. %d)", n_ranges, XGM_MAX_RANGES);
     xgm_filter_clauses cl = {};
     cl.n = n_ranges;
+    bool lists = false;
     for (uint32_t c = 0; c < n_ranges; ++c) {
+        lists = lists || ranges[c].kind != XGM_RANGE_VALUE;
         if (ranges[c].lo_ord == 0) return xgm_set_error(XGM_E_INVALID, "range clause %u: lo_ord 0 (ordinals start at 1)", c);
-        cl.lo[c] = ranges[c].lo_ord; cl.hi[c] = ranges[c].hi_ord;
+        if (ranges[c].kind > XGM_RANGE_LIST_LE) return xgm_set_error(XGM_E_INVALID, "range clause %u: kind %u", c, ranges[c].kind);
+        cl.lo[c] = ranges[c].lo_ord; cl.hi[c] = ranges[c].hi_ord; cl.kind[c] = ranges[c].kind;
     }
     {
         std::lock_guard<std::mutex> lk(idx->columns_mu);
         for (uint32_t c = 0; c < n_ranges; ++c) {
+            if (ranges[c].kind != XGM_RANGE_VALUE) {                     /* a list clause reads the slot's LIST column, whatever else the slot has */
+                auto lt = idx->list_columns.find(ranges[c].slot);
+                if (lt == idx->list_columns.end()) return XGM_UNSUPPORTED;
+                cl.ord[c] = (const uint32_t*)lt->second.head;
+                cl.ext[c] = (const uint32_t*)lt->second.ext;
+                continue;
+            }
             auto it = idx->columns.find(ranges[c].slot);
             if (it == idx->columns.end()) return XGM_UNSUPPORTED;
             cl.ord[c] = (const uint32_t*)it->second.first;
@@ -2108,10 +2195,25 @@ extern "C" int xgm_filter_build(xgm_index* idx, const xgm_value_range* ranges, u
     uint32_t* d_bits = nullptr;
     HIP_TRY(hipMalloc((void**)&d_bits, (size_t)n_padded * 4));
     unsigned long long count = 0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;                             /* xgm_index_set_profiling: a pair around the mark kernel (tools/filter_time.py) */
+    if (idx->profiling) {
+        std::lock_guard<std::mutex> lk(idx->scratch_mu);
+        if (idx->prof_used == idx->prof_events.size()) {
+            hipEvent_t a = nullptr, b = nullptr;
+            if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { if (a) hipEventDestroy(a); hipFree(d_bits); return xgm_launch_error("filter build", 0, "hipEventCreate"); }
+            idx->prof_events.push_back({a, b});
+        }
+        ev0 = (hipEvent_t)idx->prof_events[idx->prof_used].first;
+        ev1 = (hipEvent_t)idx->prof_events[idx->prof_used].second;
+        ++idx->prof_used;
+    }
     hipError_t e = hipMemsetAsync(d_count, 0, 8, sc->stream);
     if (e == hipSuccess) {
+        if (ev0) hipEventRecord(ev0, sc->stream);
         rc = xgm_launch_filter_mark(cl, idx->hdr.lastdocid, n_padded, d_bits, d_count, sc->stream);
+        if (ev1) hipEventRecord(ev1, sc->stream);
         if (rc) { hipStreamSynchronize(sc->stream); hipFree(d_bits); return rc; }
+        if (ev0) idx->last_kernel = lists ? "xgm_filter_mark_lists_kernel" : "xgm_filter_mark_kernel";
         e = hipMemcpyAsync(&count, d_count, 8, hipMemcpyDeviceToHost, sc->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(sc->stream);

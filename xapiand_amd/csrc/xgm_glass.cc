@@ -784,14 +784,14 @@ extern "C" int xgm_segment_refresh_from_glass(const char* old_segment_path, cons
  * pack_string(value of the first docid) { pack_uint(docid increase - 1) pack_string(value) }* (reference
  * backends/glass/glass_values.h:41-47, glass_values.cc:72-95).  Replaces: ValueStreamDocument / Document::get_value per
  * candidate in the matcher (matcher/matcher.cc:509-517). */
-extern "C" int xgm_glass_export_column(const char* glass_dir, uint32_t slot, const char* out_path) {
-    if (!glass_dir || !out_path) return xgm_set_error(XGM_E_INVALID, "null argument");
-    const std::string dir(glass_dir);
+/* value[d] = the slot's value of document d ("" = none), value.size() = lastdocid + 1: the chunks both column exporters read */
+static int read_slot_values(const std::string& dir, uint32_t slot, std::vector<std::string>* out) {
     GlassVersion ver;
     int rc = read_version(dir, &ver);
     if (rc) return rc;
     if (ver.last_docid > 0xFFFFFFFEull) return xgm_set_error(XGM_E_INVALID, "docids beyond 32 bits");
-    std::vector<std::string> value((size_t)ver.last_docid + 1);
+    std::vector<std::string>& value = *out;
+    value.assign((size_t)ver.last_docid + 1, std::string());
     Table post;
     if ((rc = post.open(dir + "/postlist.glass", ver.root[kTablePostlist]))) return rc;
     rc = post.walk([&](const std::string& key, const std::string& tag) -> int {
@@ -820,6 +820,13 @@ extern "C" int xgm_glass_export_column(const char* glass_dir, uint32_t slot, con
         }
         return XGM_OK;
     });
+    return rc;
+}
+
+extern "C" int xgm_glass_export_column(const char* glass_dir, uint32_t slot, const char* out_path) {
+    if (!glass_dir || !out_path) return xgm_set_error(XGM_E_INVALID, "null argument");
+    std::vector<std::string> value;
+    int rc = read_slot_values(glass_dir, slot, &value);
     if (rc) return rc;
     std::set<std::string> distinct;
     for (const std::string& v : value) if (!v.empty()) distinct.insert(v);
@@ -833,11 +840,96 @@ extern "C" int xgm_glass_export_column(const char* glass_dir, uint32_t slot, con
     }
     FILE* f = fopen(out_path, "wb");
     if (!f) return xgm_set_error(XGM_E_IO, "cannot create %s: %s", out_path, strerror(errno));
-    const uint32_t h32[4] = {slot, (uint32_t)ver.last_docid, (uint32_t)sorted.size(), 0u};
+    const uint32_t h32[4] = {slot, (uint32_t)(value.size() - 1), (uint32_t)sorted.size(), 0u};
     bool ok = fwrite("XGMCOL1", 1, 8, f) == 8 && fwrite(h32, 4, 4, f) == 4 && fwrite(ord.data(), 4, ord.size(), f) == ord.size();
     uint64_t off = 0;
     for (const std::string* v : sorted) { ok = ok && fwrite(&off, 8, 1, f) == 1; off += v->size(); }
     ok = ok && fwrite(&off, 8, 1, f) == 1;
+    for (const std::string* v : sorted) ok = ok && fwrite(v->data(), 1, v->size(), f) == v->size();
+    if (fclose(f) != 0 || !ok) return xgm_set_error(XGM_E_IO, "short write on %s", out_path);
+    return XGM_OK;
+}
+
+/* ---- list columns: a slot's values as StringLists (include/xgm.h: xgm_glass_export_list_column) ----------------------------------- */
+
+/* StringList::unserialise (reference src/serialise_list.h:333-348) over unserialise_length_and_check (src/length.cc:64-96): the
+ * elements of one slot value as (offset, length) pairs through `emit`; returns their number or XGM_E_INVALID */
+template <typename Emit>
+static int64_t split_string_list(const char* value, size_t len, Emit emit) {
+    if (len == 0) return 0;
+    if (value[0] != '\0') { emit((size_t)0, len); return 1; }
+    const uint8_t* const base = (const uint8_t*)value;
+    const uint8_t* p = base + 1;
+    const uint8_t* const end = base + len;
+    int64_t n = 0;
+    while (p != end) {
+        unsigned long long l = *p++;
+        if (l == 0xff) {
+            l = 0;
+            unsigned shift = 0;
+            uint8_t ch;
+            do {
+                if (p == end || shift > 63u) return xgm_set_error(XGM_E_INVALID, "string list: bad encoded length: insufficient data");
+                ch = *p++;
+                l |= (unsigned long long)(ch & 0x7f) << shift;
+                shift += 7;
+            } while ((ch & 0x80) == 0);
+            l += 255;
+        }
+        if (l > (unsigned long long)(end - p)) return xgm_set_error(XGM_E_INVALID, "string list: bad encoded length: length greater than data");
+        emit((size_t)(p - base), (size_t)l);
+        p += l;
+        ++n;
+    }
+    return n;
+}
+
+extern "C" int64_t xgm_debug_split_string_list(const char* value, size_t len, uint32_t* elem_begin, uint32_t* elem_len, uint32_t cap) {
+    if ((len && !value) || (cap && (!elem_begin || !elem_len))) return xgm_set_error(XGM_E_INVALID, "null argument");
+    if (len > 0xFFFFFFFFull) return xgm_set_error(XGM_E_INVALID, "value beyond 32 bits");
+    uint32_t i = 0;
+    return split_string_list(value, len, [&](size_t b, size_t l) {
+        if (i < cap) { elem_begin[i] = (uint32_t)b; elem_len[i] = (uint32_t)l; }
+        ++i;
+    });
+}
+
+extern "C" int xgm_glass_export_list_column(const char* glass_dir, uint32_t slot, const char* out_path) {
+    if (!glass_dir || !out_path) return xgm_set_error(XGM_E_INVALID, "null argument");
+    std::vector<std::string> value;
+    int rc = read_slot_values(glass_dir, slot, &value);
+    if (rc) return rc;
+    /* pass 1: the distinct elements; pass 2: their ranks, in stored order */
+    std::set<std::string> distinct;
+    uint64_t n_elem = 0;
+    for (const std::string& v : value) {
+        const int64_t n = split_string_list(v.data(), v.size(), [&](size_t b, size_t l) { distinct.insert(v.substr(b, l)); });
+        if (n < 0) return (int)n;
+        n_elem += (uint64_t)n;
+    }
+    if (n_elem > 0xFFFFFFFFull) return xgm_set_error(XGM_E_INVALID, "more than 2^32 - 1 elements in slot %u", slot);
+    std::vector<const std::string*> sorted;
+    for (const std::string& v : distinct) sorted.push_back(&v);
+    std::vector<uint32_t> off(value.size() + 1, 0u), elem;
+    elem.reserve((size_t)n_elem);
+    for (size_t d = 0; d < value.size(); ++d) {
+        const std::string& v = value[d];
+        split_string_list(v.data(), v.size(), [&](size_t b, size_t l) {
+            const std::string e = v.substr(b, l);
+            const auto it = std::lower_bound(sorted.begin(), sorted.end(), e, [](const std::string* a, const std::string& x) { return *a < x; });
+            elem.push_back((uint32_t)(it - sorted.begin()) + 1u);
+        });
+        off[d + 1] = (uint32_t)elem.size();
+    }
+    if (off[1] != 0u) return xgm_set_error(XGM_E_INVALID, "value chunk: a value for docid 0");
+    FILE* f = fopen(out_path, "wb");
+    if (!f) return xgm_set_error(XGM_E_IO, "cannot create %s: %s", out_path, strerror(errno));
+    const uint32_t h32[4] = {slot, (uint32_t)(value.size() - 1), (uint32_t)sorted.size(), 0u};
+    bool ok = fwrite("XGMLST1", 1, 8, f) == 8 && fwrite(h32, 4, 4, f) == 4 && fwrite(&n_elem, 8, 1, f) == 1 &&
+              fwrite(off.data(), 4, off.size(), f) == off.size() && fwrite(elem.data(), 4, elem.size(), f) == elem.size();
+    uint64_t voff = 0;
+    for (const std::string* v : sorted) { ok = ok && fwrite(&voff, 8, 1, f) == 1; voff += v->size(); }
+    ok = ok && fwrite(&voff, 8, 1, f) == 1;
     for (const std::string* v : sorted) ok = ok && fwrite(v->data(), 1, v->size(), f) == v->size();
     if (fclose(f) != 0 || !ok) return xgm_set_error(XGM_E_IO, "short write on %s", out_path);
     return XGM_OK;

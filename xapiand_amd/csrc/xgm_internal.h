@@ -128,6 +128,9 @@ struct xgm_index {
     std::once_flag term_order_once;
     std::vector<void*> retired_columns;                        /* replaced columns' device arrays: freed when the index closes */
     std::mutex columns_mu;
+    struct ListColumn { void* head = nullptr; void* ext = nullptr; uint32_t n_distinct = 0; };
+    std::map<uint32_t, ListColumn> list_columns;               /* value slot → (device u32 head[lastdocid + 1], u32 ext[] or null): xgm_index_attach_list_column;
+                                                                * beside `columns`, under columns_mu, replaced arrays to retired_columns */
 };
 
 int xgm_lookup_term_id(const xgm_index* idx, const char* term, size_t len, uint32_t* id);

@@ -59,10 +59,13 @@ int xgm_launch_match_sorted(const xgm_match_launch& L, const uint32_t* ord, uint
  * (a multiple of XGM_FILTER_PAD_WORDS covering lastdocid + 1 bits), all of them written; *count (device, zeroed by the caller) receives the set bits */
 #define XGM_FILTER_PAD_WORDS 64u
 struct xgm_filter_clauses {
-    const uint32_t* ord[XGM_MAX_RANGES];     /* device columns, [lastdocid + 1] */
+    const uint32_t* ord[XGM_MAX_RANGES];     /* device columns, [lastdocid + 1]; of a list clause the list column's head[] */
     uint32_t lo[XGM_MAX_RANGES], hi[XGM_MAX_RANGES];
     uint32_t n;
+    uint32_t kind[XGM_MAX_RANGES];           /* XGM_RANGE_VALUE / _LIST / _LIST_GE / _LIST_LE, the same in every lane */
+    const uint32_t* ext[XGM_MAX_RANGES];     /* a list clause's ext[] (n, then n ordinals, per multi-element document); may be NULL when no head has bit 31 */
 };
+/* a filter of XGM_RANGE_VALUE clauses alone launches xgm_filter_mark_kernel, any list kind among them xgm_filter_mark_lists_kernel */
 int xgm_launch_filter_mark(const xgm_filter_clauses& cl, uint32_t lastdocid, uint32_t n_words_padded, uint32_t* bits, unsigned long long* count,
                            hipStream_t stream);
 /* a filter's bitmap as the whole query (xgm_range.h, xgm_search_range): the first k passing documents by docid (ord NULL) or by (value, docid)

@@ -233,6 +233,19 @@ class Database:
             self._column_values = {}
         self._column_values[slot] = read_column_values(column_path)
 
+    def attach_list_column(self, path):
+        """xgm_index_attach_list_column: a slot's per-document element lists (a list column file of xgm_glass_export_list_column) into
+        HBM, for the XGM_RANGE_LIST* clauses of build_filter.  Kept beside the slot's plain column, which sorts and spies keep reading."""
+        _lib.check(_lib.lib().xgm_index_attach_list_column(self._h, _as_bytes(path)))
+
+    def attach_list_column_arrays(self, slot, off, elem, n_distinct):
+        """xgm_index_attach_list_column_ordinals: the same from memory in CSR form — the elements of document d are elem[off[d]:off[d + 1]],
+        each 1 + the rank of the element among n_distinct distinct elements, in stored order; len(off) == lastdocid + 2."""
+        import numpy as np
+        off, elem = np.ascontiguousarray(off, dtype=np.uint32), np.ascontiguousarray(elem, dtype=np.uint32)
+        p32 = C.POINTER(C.c_uint32)
+        _lib.check(_lib.lib().xgm_index_attach_list_column_ordinals(self._h, slot, off.ctypes.data_as(p32), len(off), elem.ctypes.data_as(p32), len(elem), n_distinct))
+
     def column_values(self, slot):
         vals = getattr(self, "_column_values", {}).get(slot)
         if vals is None:
@@ -240,10 +253,11 @@ class Database:
         return vals
 
     def build_filter(self, ranges):
-        """xgm_filter_build: the documents whose ordinals pass EVERY (slot, lo_ord, hi_ord) of `ranges` (1 .. 4 clauses on attached columns;
-        column_ord_range makes the ordinals from byte bounds), as a bitmap on the device → Filter."""
+        """xgm_filter_build: the documents whose ordinals pass EVERY (slot, lo_ord, hi_ord) or (slot, lo_ord, hi_ord, kind) of `ranges`
+        (1 .. 4 clauses on attached columns; column_ord_range makes the ordinals from byte bounds), as a bitmap on the device → Filter.
+        kind: _lib.XGM_RANGE_VALUE (the default, a plain column) or XGM_RANGE_LIST / _LIST_GE / _LIST_LE on a list column."""
         n = len(ranges)
-        arr = (_lib.ValueRange * max(1, n))(*[_lib.ValueRange(s, lo, hi, 0) for s, lo, hi in ranges])
+        arr = (_lib.ValueRange * max(1, n))(*[_lib.ValueRange(r[0], r[1], r[2], r[3] if len(r) > 3 else _lib.XGM_RANGE_VALUE) for r in ranges])
         h, nd = C.c_void_p(), C.c_uint64()
         _lib.check(_lib.lib().xgm_filter_build(self._h, arr, n, C.byref(h), C.byref(nd)))
         return Filter(h, nd.value, (self._info.lastdocid + 32) // 32)
@@ -422,16 +436,33 @@ def plan(db, query, first, maxitems, check_at_least=0, weight=None, global_stats
 
 
 def read_column_values(path):
-    """The distinct values of a column file (xgm_glass_export_column), ascending: ordinal o > 0 of a hit is values[o - 1]."""
+    """The distinct values of a column file (xgm_glass_export_column), ascending: ordinal o > 0 of a hit is values[o - 1].  Of a list
+    column file (xgm_glass_export_list_column) the distinct ELEMENTS, which its ordinals rank."""
     import struct
     b = open(path, "rb").read()
-    if b[:8] != b"XGMCOL1\0":
+    if b[:8] not in (b"XGMCOL1\0", b"XGMLST1\0"):
         raise ValueError("%s is not a column file" % path)
     slot, lastdocid, n, _ = struct.unpack_from("<4I", b, 8)
-    o = 24 + 4 * (lastdocid + 1)
+    if b[:8] == b"XGMLST1\0":
+        o = 32 + 4 * (lastdocid + 2 + struct.unpack_from("<Q", b, 24)[0])
+    else:
+        o = 24 + 4 * (lastdocid + 1)
     off = struct.unpack_from("<%dQ" % (n + 1), b, o)
     base = o + 8 * (n + 1)
     return [b[base + off[i]:base + off[i + 1]] for i in range(n)]
+
+
+def read_list_column(path):
+    """A list column file (xgm_glass_export_list_column) → (slot, off, elem, n_distinct): the CSR Database.attach_list_column_arrays takes."""
+    import struct
+    b = open(path, "rb").read()
+    if b[:8] != b"XGMLST1\0":
+        raise ValueError("%s is not a list column file" % path)
+    slot, lastdocid, n, _ = struct.unpack_from("<4I", b, 8)
+    n_elem = struct.unpack_from("<Q", b, 24)[0]
+    off = list(struct.unpack_from("<%dI" % (lastdocid + 2), b, 32))
+    elem = list(struct.unpack_from("<%dI" % n_elem, b, 32 + 4 * (lastdocid + 2)))
+    return slot, off, elem, n
 
 
 def search_sorted(db, planned, sort_by, slot, reverse=False):
