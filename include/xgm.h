@@ -811,6 +811,11 @@ int64_t xgm_debug_read_container(xgm_index*, uint32_t term_id, uint32_t stripe, 
  * or the index keeps no summary (XGM_NO_WDF_SUMMARY at open, or no memory for it); < 0 on error.  Launches no kernel. */
 int xgm_debug_read_wdf_summary(xgm_index*, uint32_t term_id, uint32_t stripe, uint64_t* out);
 
+/* Diagnostics: does the term hold a posting of wdf 0 (a boolean posting), as the conjunction kernels see it: the flag that decides whether a clear bit of
+ * the containers' wdf >= 2 plane means wdf = 1.  Returns 1 and sets *out to 0 or 1; 0, *out unchanged, when the term has no containers or the index keeps no
+ * such flags (no memory for them); < 0 on error.  Launches no kernel. */
+int xgm_debug_read_term_wdf0(xgm_index*, uint32_t term_id, uint32_t* out);
+
 /* Diagnostics: copy a term's flat posting arrays to the host: docids, wdf bytes and, into pos when not NULL and the index keeps them
  * (*has_pos = 1), each posting's position-entry offset relative to the term.  Returns the number of postings, 0 when the term has no flat
  * array, or < 0.  Launches no kernel. */

@@ -190,6 +190,7 @@ _API = [
     ("xgm_debug_read_positions", C.c_int64, [C.c_void_p, C.c_uint32, _P(C.c_uint32), C.c_uint64]),
     ("xgm_debug_read_container", C.c_int64, [C.c_void_p, C.c_uint32, C.c_uint32, _P(C.c_ubyte), C.c_uint64, _P(C.c_uint32)]),
     ("xgm_debug_read_wdf_summary", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _P(C.c_uint64)]),
+    ("xgm_debug_read_term_wdf0", C.c_int, [C.c_void_p, C.c_uint32, _P(C.c_uint32)]),
     ("xgm_debug_read_flat", C.c_int64, [C.c_void_p, C.c_uint32, _P(C.c_uint32), _P(C.c_ubyte), _P(C.c_uint32), C.c_uint64, _P(C.c_uint32)]),
     ("xgm_debug_plan_us", C.c_double, [C.c_void_p, _P(QueryDesc), _P(GlobalStats), C.c_uint32, C.c_uint32]),
     ("xgm_debug_batch_launches", C.c_int, [C.c_void_p, _P(Query), C.c_uint32, C.c_char_p, C.c_uint32]),

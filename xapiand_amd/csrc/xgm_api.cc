@@ -208,7 +208,7 @@ static void fill_view(xgm_index* idx) {
     v.stripe_bits = idx->hdr.stripe_bits;
     v.lastdocid = idx->hdr.lastdocid;
     v.dense_id = nullptr; v.dense_dir = nullptr; v.dense_data = nullptr; v.n_dense = 0; v.dense_pos = 0; v.dense_plane = 0;
-    v.dense_p2 = nullptr; v.bit_screen = 0;
+    v.dense_p2 = nullptr; v.bit_screen = 0; v.exact_wdf = 0; v.dense_wdf0 = nullptr; v.reserved_ = 0;
     v.doclen_narrow = nullptr; v.doclen_narrow_bits = 0; v.doclen_base = 0;
     v.flat_off = nullptr; v.flat_did = nullptr; v.flat_wdf = nullptr; v.flat_pos = nullptr;
     v.n_stripes = (idx->hdr.lastdocid >> idx->hdr.stripe_bits) + 1u;
@@ -291,6 +291,7 @@ extern "C" void xgm_index_close(xgm_index* idx) {
     if (idx->d_flat_pos) hipFree(idx->d_flat_pos);
     if (idx->d_dense_dir) hipFree(idx->d_dense_dir);
     if (idx->d_dense_p2) hipFree(idx->d_dense_p2);
+    if (idx->d_dense_wdf0) hipFree(idx->d_dense_wdf0);
     if (idx->d_dense_data) hipFree(idx->d_dense_data);
     for (auto& c : idx->columns) if (c.second.first) hipFree(c.second.first);
     for (auto& c : idx->list_columns) { if (c.second.head) hipFree(c.second.head); if (c.second.ext) hipFree(c.second.ext); }
@@ -3263,6 +3264,23 @@ extern "C" int xgm_debug_read_wdf_summary(xgm_index* idx, uint32_t term_id, uint
     uint64_t w = 0;
     HIP_TRY(hipMemcpy(&w, (const uint64_t*)idx->d_dense_p2 + (size_t)d * idx->view.n_stripes + stripe, 8, hipMemcpyDeviceToHost));
     *out = w;
+    return 1;
+}
+
+/* Does the term hold a posting of wdf 0, as the kernels see it (xgm_seg_dev::dense_wdf0)?  Returns 1 and sets *out to 0 / 1; 0, *out unchanged, when the
+ * term has no containers or the index keeps no such flags.  Copies only: no kernel runs. */
+extern "C" int xgm_debug_read_term_wdf0(xgm_index* idx, uint32_t term_id, uint32_t* out) {
+    if (!idx || !out) return xgm_set_error(XGM_E_INVALID, "null argument");
+    if (term_id >= idx->hdr.n_terms) return xgm_set_error(XGM_E_INVALID, "term id out of range");
+    int rc = use_device(idx->device);
+    if (rc) return rc;
+    if (!idx->view.n_dense || !idx->d_dense_id || !idx->d_dense_wdf0) return 0;
+    uint32_t d = 0xFFFFFFFFu, f = 0;
+    HIP_TRY(hipMemcpy(&d, (const uint32_t*)idx->d_dense_id + term_id, 4, hipMemcpyDeviceToHost));
+    if (d == 0xFFFFFFFFu) return 0;
+    if (d >= idx->view.n_dense) return xgm_set_error(XGM_E_INVALID, "dense id %u out of range", d);
+    HIP_TRY(hipMemcpy(&f, (const uint32_t*)idx->d_dense_wdf0 + d, 4, hipMemcpyDeviceToHost));
+    *out = f ? 1u : 0u;
     return 1;
 }
 

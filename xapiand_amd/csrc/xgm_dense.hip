@@ -49,7 +49,7 @@ __global__ void k_dense_count(xgm_seg_dev seg, const uint32_t* __restrict__ dens
 /* one workgroup per (stripe, dense term): decode the run, write the bitmap and the per-slot wdf+1 bytes */
 __global__ __launch_bounds__(256) void k_dense_fill(xgm_seg_dev seg, const uint32_t* __restrict__ dense_terms, uint32_t n_stripes,
                                                     const uint32_t* __restrict__ dir, unsigned char* __restrict__ data, int with_pos,
-                                                    uint32_t* __restrict__ wdf_max, unsigned long long* __restrict__ p2) {
+                                                    uint32_t* __restrict__ wdf_max, unsigned long long* __restrict__ p2, uint32_t* __restrict__ wdf0) {
     __shared__ uint32_t bitmap[256];
     __shared__ uint32_t bitmap2[256];     /* wdf >= 2 */
     __shared__ uint32_t wmax_s;
@@ -82,6 +82,7 @@ __global__ __launch_bounds__(256) void k_dense_fill(xgm_seg_dev seg, const uint3
     const uint32_t rb = run[0], nb = run[1] - rb;
     uint32_t* stage = stage_all + wave * kStage;
     uint32_t wmax = 0;
+    bool zero = false;                    /* a posting of wdf 0 met (xgm_seg_dev::dense_wdf0) */
     for (uint32_t j = wave; j < nb; j += 4u) {
         const uint32_t b = rb + j, meta = seg.blk_meta[b], first = seg.blk_first[b];
         const uint32_t n = XGM_META_COUNT(meta), bwg = XGM_META_BWG(meta), bww = XGM_META_BWW(meta);
@@ -107,7 +108,9 @@ __global__ __launch_bounds__(256) void k_dense_fill(xgm_seg_dev seg, const uint3
         if (v0) { const uint32_t sl = d0 & (W - 1u); atomicOr(&bitmap[sl >> 5], 1u << (sl & 31u)); if (w0 >= 2u) atomicOr(&bitmap2[sl >> 5], 1u << (sl & 31u)); wdf_out[sl] = (unsigned char)(w0 + 1u); if (with_pos) atomicMin(&pbase[sl >> 6], pex); if (w0 != 1u) atomicOr(&sum_s[sl >> (SB - 1u)], 1u << ((sl >> (SB - 6u)) & 31u)); }
         if (v1) { const uint32_t sl = d1 & (W - 1u); atomicOr(&bitmap[sl >> 5], 1u << (sl & 31u)); if (w1 >= 2u) atomicOr(&bitmap2[sl >> 5], 1u << (sl & 31u)); wdf_out[sl] = (unsigned char)(w1 + 1u); if (with_pos) atomicMin(&pbase[sl >> 6], pex + w0); if (w1 != 1u) atomicOr(&sum_s[sl >> (SB - 1u)], 1u << ((sl >> (SB - 6u)) & 31u)); }
         wmax = max(wmax, max(w0, w1));
+        zero = zero || (v0 && w0 == 0u) || (v1 && w1 == 0u);
     }
+    if (wdf0 && __ballot(zero) != 0ull && lane == 0u) atomicOr(&wdf0[d], 1u);
     if (wmax) atomicMax(&wmax_s, wmax);
     __syncthreads();
     if (tid < NW) reinterpret_cast<uint32_t*>(cont)[tid] = bitmap[tid];
@@ -267,7 +270,9 @@ int xgm_build_dense(xgm_index* idx) {
 static int build_containers(xgm_index* idx) {
     idx->view.dense_id = nullptr; idx->view.dense_dir = nullptr; idx->view.dense_data = nullptr;
     idx->view.n_dense = 0; idx->view.dense_plane = 0; idx->view.dense_p2 = nullptr; idx->view.bit_screen = 0;
+    idx->view.exact_wdf = 0; idx->view.dense_wdf0 = nullptr; idx->view.reserved_ = 0;
     if (idx->d_dense_p2) { hipFree(idx->d_dense_p2); idx->d_dense_p2 = nullptr; }
+    if (idx->d_dense_wdf0) { hipFree(idx->d_dense_wdf0); idx->d_dense_wdf0 = nullptr; }
     idx->term_wdfmax.clear();
     const uint32_t SB = idx->hdr.stripe_bits;
     const uint32_t n_stripes = (idx->hdr.lastdocid >> SB) + 1u;
@@ -327,8 +332,13 @@ static int build_containers(xgm_index* idx) {
             if (idx->d_dense_p2) { hipFree(idx->d_dense_p2); idx->d_dense_p2 = nullptr; }
         }
     }
+    /* one word per dense term: does it hold a posting of wdf 0 (xgm_seg_dev::dense_wdf0)?  An accelerator as well: without it xgm_dense_unit keeps to the summary */
+    if (hipMalloc(&idx->d_dense_wdf0, (size_t)n_dense * 4) != hipSuccess || hipMemset(idx->d_dense_wdf0, 0, (size_t)n_dense * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        if (idx->d_dense_wdf0) { hipFree(idx->d_dense_wdf0); idx->d_dense_wdf0 = nullptr; }
+    }
     hipLaunchKernelGGL(k_dense_fill, dim3(n_stripes, n_dense), dim3(256), 0, 0, idx->view, d_terms, n_stripes, (const uint32_t*)idx->d_dense_dir,
-                       (unsigned char*)idx->d_dense_data, with_pos, d_wmax, (unsigned long long*)idx->d_dense_p2);
+                       (unsigned char*)idx->d_dense_data, with_pos, d_wmax, (unsigned long long*)idx->d_dense_p2, (uint32_t*)idx->d_dense_wdf0);
     DN_TRY(hipGetLastError());
     DN_TRY(hipDeviceSynchronize());
     wmax.resize(n_dense);
@@ -336,7 +346,7 @@ static int build_containers(xgm_index* idx) {
     idx->term_wdfmax.assign(idx->term_wdfub.begin(), idx->term_wdfub.end());
     for (uint32_t d = 0; d < n_dense; ++d)
         if (wmax[d] && wmax[d] < idx->term_wdfmax[dense_terms[d]]) idx->term_wdfmax[dense_terms[d]] = wmax[d];
-    idx->dense_bytes = dense_id.size() * 4 + dir.size() * 4 + units * 16 + (idx->d_dense_p2 ? dir.size() * 8 : 0);
+    idx->dense_bytes = dense_id.size() * 4 + dir.size() * 4 + units * 16 + (idx->d_dense_p2 ? dir.size() * 8 : 0) + (idx->d_dense_wdf0 ? (size_t)n_dense * 4 : 0);
     idx->device_bytes += idx->dense_bytes;
     idx->view.dense_id = (const uint32_t*)idx->d_dense_id;
     idx->view.dense_dir = (const uint32_t*)idx->d_dense_dir;
@@ -346,6 +356,9 @@ static int build_containers(xgm_index* idx) {
     idx->view.dense_plane = plane_off;
     idx->view.dense_p2 = (const unsigned long long*)idx->d_dense_p2;
     idx->view.bit_screen = getenv("XGM_NO_BIT_SCREEN") ? 0u : 1u;      /* A/B switch: xgm_flat_unit screens by the wdf byte again */
+    idx->view.dense_wdf0 = (const uint32_t*)idx->d_dense_wdf0;
+    /* A/B switch XGM_NO_EXACT_WDF: crowded stripes keep to the summary.  The candidate ring carries the plane bits above a unit-relative docid of 5 + SB bits */
+    idx->view.exact_wdf = (!getenv("XGM_NO_EXACT_WDF") && idx->d_dense_wdf0 && idx->d_dense_p2 && plane_off && 5u + SB <= 28u) ? 1u : 0u;
     idx->dense_min_df = (uint64_t)min_avg * n_stripes;
     hipFree(d_terms); hipFree(d_cnt); hipFree(d_wmax);
     return XGM_OK;
@@ -357,6 +370,7 @@ fail:
     if (idx->d_dense_dir) { hipFree(idx->d_dense_dir); idx->d_dense_dir = nullptr; }
     if (idx->d_dense_data) { hipFree(idx->d_dense_data); idx->d_dense_data = nullptr; }
     if (idx->d_dense_p2) { hipFree(idx->d_dense_p2); idx->d_dense_p2 = nullptr; }
-    idx->view.dense_p2 = nullptr;
+    if (idx->d_dense_wdf0) { hipFree(idx->d_dense_wdf0); idx->d_dense_wdf0 = nullptr; }
+    idx->view.dense_p2 = nullptr; idx->view.dense_wdf0 = nullptr; idx->view.exact_wdf = 0;
     return rc;
 }

@@ -31,6 +31,12 @@ constexpr uint32_t kDenseRing = 256;       /* candidate ring (docids) */
 #define XGM_DENSE_PREFILTER_MIN 48
 #endif
 constexpr uint32_t kDensePrefilterMin = XGM_DENSE_PREFILTER_MIN;   /* matches in a stripe from which the wdf >= 2 bitmaps are worth their T KiB */
+#ifndef XGM_DENSE_EXACT_MIN
+#define XGM_DENSE_EXACT_MIN XGM_DENSE_PREFILTER_MIN                /* A/B switch (tools/ab_build.sh) */
+#endif
+constexpr uint32_t kDenseExactMin = XGM_DENSE_EXACT_MIN;           /* plain conjunctions: matches in a stripe (before the prefilter drops any) from which wdf = 1 is taken from those
+                                                                     bitmaps, exact per document, instead of the 128-slot summary (an EXACT STRIPE; xgm_seg_dev::exact_wdf) */
+constexpr uint32_t kDenseExactLane = 16;                           /* candidates per lane and stripe whose plane bits the lane's packed code holds (4 bits each); the rest consult the summary */
 
 #ifndef XGM_DENSE_WORD_MAJOR
 #define XGM_DENSE_WORD_MAJOR 1                                     /* A/B switch (tools/ab_build.sh): the positional body's bitmaps word-major, see load_words */
@@ -62,10 +68,14 @@ constexpr size_t kDenseCoreBytes = (size_t)kDenseCap * 8 + (size_t)kDenseCap * 4
 /* plain conjunctions: the wdf != 1 summary words (xgm_seg_dev::dense_p2) of the unit's (stripe, term) pairs, as u32 [kDenseSpg][2 halves][kDenseT] — the
  * four terms' bits of a candidate's slot are ONE 16-byte LDS read; xgm_flat_unit keeps them as u64 [kDenseT][kDenseSpg] behind its offsets */
 constexpr size_t kDenseP2Bytes = (size_t)kDenseSpg * kDenseT * 8;
+/* plain conjunctions: every lane's packed plane bits (kDenseExactLane candidates x 4 bits) while the consumer runs — parked here between two calls of the
+ * producer, so that they hold no registers across the round loop */
+constexpr size_t kDenseXcBytes = 64 * 8;
+static_assert(4u * kDenseExactLane == 64u, "a lane's packed code is one u64");
 /* phrase: + the survivor queue and the survivors' positions staged for the predicates, u16 [T][kPosFast][64 lanes] (xgm_posfilter.h).
  * Inside xgm_andw_kernel the wave's slice (andw_wave_bytes) is larger than this for any tab_terms >= T. */
 __host__ __device__ constexpr size_t dense_wave_bytes(bool phrase, uint32_t terms = kDenseT) {
-    return kDenseCoreBytes + (phrase ? (size_t)kDenseSq * 16 + (size_t)terms * kPosFast * 64 * 2 : kDenseP2Bytes);
+    return kDenseCoreBytes + (phrase ? (size_t)kDenseSq * 16 + (size_t)terms * kPosFast * 64 * 2 : kDenseP2Bytes + kDenseXcBytes);
 }
 
 typedef uint32_t dense_u4 __attribute__((ext_vector_type(4)));
@@ -181,6 +191,15 @@ __device__ __forceinline__ void dense_topk_sort(uint64_t* w, uint32_t* d, uint32
     wave_lds_fence();
 }
 
+/* The sort's element indices depend on the lane alone, and the compiler computes them once per kernel and keeps them — in registers, or in scratch — across
+ * everything else.  A lane id it cannot see through keeps that arithmetic inside the (rare) sort. */
+__device__ __forceinline__ uint32_t dense_sort_lane(uint32_t lane) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(lane));
+#endif
+    return lane;
+}
+
 /* wk: the unit, wave-uniform.  base: the wave's LDS slice. */
 template <bool PHRASE, bool TALLY, bool LIST = false, bool ALL = false>
 __device__ __forceinline__ void xgm_dense_unit(const xgm_seg_dev& seg, const xgm_dev_query* __restrict__ queries, const xgm_work wk0, unsigned char* base,
@@ -243,8 +262,14 @@ __device__ __forceinline__ void xgm_dense_unit(const xgm_seg_dev& seg, const xgm
     /* plain only: the containers' wdf != 1 summaries, [kDenseSpg][low / high half][kDenseT].  A candidate is a member of every term (the AND of the bitmaps says
      * so): where the summary bit of its slot is clear its wdf is 1 and the byte is not fetched (issue).  No summary (wave-uniform): every byte is. */
     uint32_t* p2s = reinterpret_cast<uint32_t*>(base + kDenseCoreBytes);
+    unsigned long long* xcs = reinterpret_cast<unsigned long long*>(base + kDenseCoreBytes + kDenseP2Bytes);      /* plain only: the lanes' packed plane bits, see kDenseXcBytes */
     bool use_p2 = false;
     if constexpr (!PHRASE) use_p2 = seg.dense_p2 != nullptr;
+    /* plain only, exact stripes: a term WITHOUT a posting of wdf 0 (xgm_seg_dev::dense_wdf0) has wdf = 1 exactly where its bits2 bit is clear.  The ring then
+     * holds unit-relative docids (5 + SB <= 28 bits, checked at open) under four bits per candidate: bit 28 + t clear = term t's wdf is 1, no byte asked for */
+    bool use_exact = false;
+    if constexpr (!PHRASE) use_exact = use_p2 && rfl32(seg.exact_wdf) != 0u;
+    uint32_t z_mask = 0xFu;                                        /* terms whose clear plane bit proves nothing (wdf 0 or 1): they keep to the summary */
 
     const uint32_t s_begin = wk.s_begin, s_end = wk.s_end;
     const bool empty = (q.flags & XGM_QF_EMPTY) || s_begin >= s_end || k == 0;
@@ -276,6 +301,20 @@ __device__ __forceinline__ void xgm_dense_unit(const xgm_seg_dev& seg, const xgm
         if constexpr (!PHRASE) { if (use_p2) { p2s[x * (2u * kDenseT) + t] = (uint32_t)p2w; p2s[x * (2u * kDenseT) + kDenseT + t] = (uint32_t)(p2w >> 32); } }
     }
     if (TALLY) { cn_aux += T * n_local * (use_p2 ? 3u : 1u); }
+    if constexpr (!PHRASE) {
+        if (use_exact) {
+#pragma unroll
+            for (uint32_t t = 0; t < kDenseT; ++t) {
+                if (t < T) {
+                    const uint32_t id = rfl32(q.term_id[t]);
+                    const uint32_t dn = id != 0xFFFFFFFFu ? rfl32(seg.dense_id[id]) : 0xFFFFFFFFu;
+                    if (dn != 0xFFFFFFFFu && rfl32(seg.dense_wdf0[dn]) == 0u) z_mask &= ~(1u << t);
+                }
+            }
+            if (TALLY) { cn_aux += T; }
+        }
+    }
+    const uint32_t ring_base = use_exact ? s_begin << SB : 0u;     /* what a ring entry's docid is relative to */
     wave_lds_fence();
 
     /* PHRASE: the units of a query share what they learn (see xgm_andw_kernel): a 256-bucket histogram of the weights of the
@@ -389,7 +428,7 @@ __device__ __forceinline__ void xgm_dense_unit(const xgm_seg_dev& seg, const xgm
      * soon as k matches are held) */
     auto make_room = [&]() {
         if (__builtin_expect(tkn + 64u > kDenseCap || (PHRASE && !theta_valid && tkn >= k), 0)) {      /* (rare: the allocator keeps its spills out of the round loop) */
-            dense_topk_sort(tk_w, tk_d, lane);
+            dense_topk_sort(tk_w, tk_d, PHRASE ? lane : dense_sort_lane(lane));
             tkn = tkn < k ? tkn : k;
             if (tkn == k) { theta_valid = true; theta_w = tk_w[k - 1]; theta_d = tk_d[k - 1]; }
 #pragma unroll
@@ -649,8 +688,11 @@ __device__ __forceinline__ void xgm_dense_unit(const xgm_seg_dev& seg, const xgm
         const uint32_t c_a = XGM_CLK();
         const bool valid = lane < n;
         /* lanes beyond n repeat the round's first candidate: every lane loads, no branch around the gathers */
-        const uint32_t did = ring[(head + (valid ? lane : 0u)) & (kDenseRing - 1u)];
+        uint32_t did = ring[(head + (valid ? lane : 0u)) & (kDenseRing - 1u)];
         wave_lds_fence();                                          /* the producer may write these ring entries again from here on */
+        /* plain: bit t = this lane may have to ask for term t's byte — a live lane, and on an exact stripe the candidate's plane bit (z_mask's terms: 1) */
+        uint32_t xbits = valid ? 0xFu : 0u;
+        if constexpr (!PHRASE) { if (use_exact) { xbits = valid ? did >> 28 : 0u; did = (did & 0x0FFFFFFFu) + ring_base; } }
         head = (head + n) & (kDenseRing - 1u);
         pend -= n;
         const uint32_t x = (did >> SB) - s_begin, slot = did & (W - 1u);
@@ -659,13 +701,12 @@ __device__ __forceinline__ void xgm_dense_unit(const xgm_seg_dev& seg, const xgm
         const uint32_t ro[kDenseT] = {ro4.x, ro4.y, ro4.z, ro4.w};
         /* plain: which bytes have to be fetched — the summary bit of the candidate's slot, per term (the half of the words that holds it: one 16-byte
          * LDS read); without a summary every lane asks, the idle ones included, as ever */
-        uint32_t ask[kDenseT] = {1u, 1u, 1u, 1u};
+        uint32_t ask[kDenseT] = {1u, 1u, 1u, 1u};                  /* (bit 0 counts) */
         if constexpr (!PHRASE) {
             if (use_p2) {
                 const uint32_t j = slot >> (SB - 6u);
                 const dense_u4 pw = *reinterpret_cast<const dense_u4*>(&p2s[x * (2u * kDenseT) + (j >> 5) * kDenseT]);
-                const uint32_t live = valid ? 1u : 0u;
-                ask[0] = (pw.x >> (j & 31u)) & live; ask[1] = (pw.y >> (j & 31u)) & live; ask[2] = (pw.z >> (j & 31u)) & live; ask[3] = (pw.w >> (j & 31u)) & live;
+                ask[0] = (pw.x >> (j & 31u)) & xbits; ask[1] = (pw.y >> (j & 31u)) & (xbits >> 1); ask[2] = (pw.z >> (j & 31u)) & (xbits >> 2); ask[3] = (pw.w >> (j & 31u)) & (xbits >> 3);
             }
         }
 #pragma unroll
@@ -676,7 +717,7 @@ __device__ __forceinline__ void xgm_dense_unit(const xgm_seg_dev& seg, const xgm
                     wv[t] = seg.dense_data[(size_t)ro[t < T ? t : T - 1u] * 16 + (size_t)NW * 4 + slot];
                 } else {
                     wv[t] = 2u;                                    /* wdf 1: what the byte would read */
-                    if (ask[t]) wv[t] = seg.dense_data[(size_t)ro[t < T ? t : T - 1u] * 16 + (size_t)NW * 4 + slot];
+                    if (ask[t] & 1u) wv[t] = seg.dense_data[(size_t)ro[t < T ? t : T - 1u] * 16 + (size_t)NW * 4 + slot];
                 }
             }
         }
@@ -693,9 +734,9 @@ __device__ __forceinline__ void xgm_dense_unit(const xgm_seg_dev& seg, const xgm
 #pragma unroll
                 for (uint32_t t = 0; t < kDenseT; ++t) {
                     if (t < T) {
-                        const uint64_t am = __ballot(ask[t] != 0u), below = am & ((1ull << lane) - 1ull);
+                        const uint64_t am = __ballot((ask[t] & 1u) != 0u), below = am & ((1ull << lane) - 1ull);
                         const uint32_t prev = (uint32_t)__shfl((int)did, below ? 63 - (int)__builtin_clzll(below) : (int)lane);
-                        cn_probe += (uint32_t)__popcll(__ballot(ask[t] != 0u && (below == 0ull || (prev >> 6) != (did >> 6))));
+                        cn_probe += (uint32_t)__popcll(__ballot((ask[t] & 1u) != 0u && (below == 0ull || (prev >> 6) != (did >> 6))));
                         cn_probe_raw += (uint32_t)__popcll(am);
                     }
                 }
@@ -739,6 +780,8 @@ __device__ __forceinline__ void xgm_dense_unit(const xgm_seg_dev& seg, const xgm
     while ((sl < n_local || pend) && !(LIST && pf.done)) {
         const uint32_t c_p0 = XGM_CLK();
         if (sl < n_local && pend < kDenseRefill) {
+            unsigned long long xcode = ~0ull; (void)xcode;         /* plain, use_exact: the packed plane bits of this lane's next candidates, shifted out as they are emitted */
+            if constexpr (!PHRASE) { if (use_exact && !fresh) xcode = xcs[lane]; }
             if (fresh) {
                 uint32_t cnt = (uint32_t)(__popc(m.x) + __popc(m.y) + __popc(m.z) + __popc(m.w));
                 /* the threshold a candidate has to reach: the unit's own k-th best and — positional queries — the query-wide bound */
@@ -746,6 +789,26 @@ __device__ __forceinline__ void xgm_dense_unit(const xgm_seg_dev& seg, const xgm
                 if (PHRASE && theta_glob > th_bits) th_bits = theta_glob;
                 {
                     if (!PHRASE) matches += cnt;                   /* a bit of the AND is a match, weighed or not (positional: a match once its positions pass) */
+                    /* plain, an exact stripe (counted before the prefilter drops anything — its own trigger): the T planes are loaded here, threshold or not;
+                     * the prefilter below uses the same registers when its conditions hold */
+                    dense_u4 b2[kDenseT];
+                    bool have_b2 = false, exact_stripe = false, have_total = false;
+                    uint32_t total = 0u;
+                    if constexpr (!PHRASE) {
+                        if (use_exact) {
+                            total = rl32(wave_incl_scan(cnt), 63); have_total = true;
+                            exact_stripe = total >= kDenseExactMin;
+                            if (exact_stripe) {
+#pragma unroll
+                                for (uint32_t t = 0; t < kDenseT; ++t) {
+                                    const uint32_t off = off_of(t, sl);
+                                    b2[t] = load_words(seg.dense_data + (size_t)off * 16 + seg.dense_plane);
+                                }
+                                if (TALLY) { cn_bmpw += T * NW; }
+                                have_b2 = true;
+                            }
+                        }
+                    }
                     /* A stripe crowded with matches, the unit's k-th best known: most of them cannot reach it, and the containers'
                      * second bitmap (documents whose wdf is >= 2) says so without a probe.  A document whose wdf is 1 for the
                      * terms outside S weighs at most UB(S) = sum of ub[t] over S + ub1[t] over the rest (the planner's bounds: the
@@ -754,14 +817,15 @@ __device__ __forceinline__ void xgm_dense_unit(const xgm_seg_dev& seg, const xgm
                      * (an up-set: every superset of a kept class is kept). */
                     /* (no branch hint here: for two-term conjunctions of frequent terms nearly every stripe takes it — marked cold, the allocator
                      *  parked its spills in this block and AND-2 lost 12 %) */
-                    if (!ALL && th_bits && seg.dense_plane && u_ub1_all < __longlong_as_double((long long)th_bits) && rl32(wave_incl_scan(cnt), 63) >= kDensePrefilterMin) {
-                        dense_u4 b2[kDenseT];
+                    if (!ALL && th_bits && seg.dense_plane && u_ub1_all < __longlong_as_double((long long)th_bits) && (have_total ? total : rl32(wave_incl_scan(cnt), 63)) >= kDensePrefilterMin) {
+                        if (!have_b2) {
 #pragma unroll
-                        for (uint32_t t = 0; t < kDenseT; ++t) {
-                            const uint32_t off = off_of(t, sl);
-                            b2[t] = load_words(seg.dense_data + (size_t)off * 16 + seg.dense_plane);
+                            for (uint32_t t = 0; t < kDenseT; ++t) {
+                                const uint32_t off = off_of(t, sl);
+                                b2[t] = load_words(seg.dense_data + (size_t)off * 16 + seg.dense_plane);
+                            }
+                            if (TALLY) { cn_bmpw += T * NW; }
                         }
-                        if (TALLY) { cn_bmpw += T * NW; }
                         const double th = __longlong_as_double((long long)th_bits);
                         double u_ub[kDenseT], u_ub1[kDenseT];
 #pragma unroll
@@ -783,6 +847,25 @@ __device__ __forceinline__ void xgm_dense_unit(const xgm_seg_dev& seg, const xgm
                         if (PHRASE && kept != cnt) pos_pruned = true;     /* dropped untested: the positional match count is a lower bound */
                         cnt = kept;
                     }
+                    /* the plane bits of this lane's first kDenseExactLane candidates, four per candidate in the order the enumeration below emits them; the
+                     * planes themselves die here.  Ones shift in from the top: a lane's further candidates, and every candidate of other stripes, consult the summary */
+                    if constexpr (!PHRASE) {
+                        if (exact_stripe) {                          /* (xcode is all ones here: a fresh stripe starts from the initial value) */
+                            const uint32_t mw[4] = {m.x, m.y, m.z, m.w};
+                            uint32_t sh = 0u;
+#pragma unroll
+                            for (uint32_t g = 0; g < 4u; ++g) {
+                                uint32_t rest = mw[g];
+                                while (rest && sh < 4u * kDenseExactLane) {
+                                    const uint32_t bit = (uint32_t)__ffs(rest) - 1u;
+                                    const uint32_t nib = (((b2[0][g] >> bit) & 1u) | (((b2[1][g] >> bit) & 1u) << 1) | (((b2[2][g] >> bit) & 1u) << 2) | (((b2[3][g] >> bit) & 1u) << 3)) | z_mask;
+                                    xcode &= ~((unsigned long long)(nib ^ 0xFu) << sh);
+                                    rest &= rest - 1u;
+                                    sh += 4u;
+                                }
+                            }
+                        }
+                    }
                 }
                 if (kWordMajor) {
                     /* docid order = component 0 of every lane, then component 1, ...: a prefix sum per component */
@@ -803,11 +886,16 @@ __device__ __forceinline__ void xgm_dense_unit(const xgm_seg_dev& seg, const xgm
             const uint32_t take_n = n_total - done < room ? n_total - done : room;
             const uint32_t lim = done + take_n;
             const uint32_t wbase = tail - done;                    /* ring position of ordinal 0 (mod the ring) */
-            const uint32_t dbase = ((s_begin + sl) << SB) + lane * (kWordMajor ? 32u : 128u);
+            const uint32_t dbase = ((s_begin + sl) << SB) + lane * (kWordMajor ? 32u : 128u) - ring_base;
 #define XGM_DENSE_EMIT(MW, O, D)                                                                          \
             while (MW && O < lim) {                                                                       \
                 const uint32_t bit = (uint32_t)__ffs(MW) - 1u;                                            \
-                ring[(wbase + O) & (kDenseRing - 1u)] = dbase + (D) + bit;                                \
+                if constexpr (!PHRASE) {                                                                  \
+                    ring[(wbase + O) & (kDenseRing - 1u)] = (dbase + (D) + bit) | (use_exact ? (uint32_t)xcode << 28 : 0u); \
+                    xcode = (xcode >> 4) | (0xFull << 60);                                                \
+                } else {                                                                                  \
+                    ring[(wbase + O) & (kDenseRing - 1u)] = dbase + (D) + bit;                            \
+                }                                                                                         \
                 MW &= MW - 1u;                                                                            \
                 ++O;                                                                                      \
             }
@@ -823,6 +911,7 @@ __device__ __forceinline__ void xgm_dense_unit(const xgm_seg_dev& seg, const xgm
                 XGM_DENSE_EMIT(m.w, o, 96u)
             }
 #undef XGM_DENSE_EMIT
+            if constexpr (!PHRASE) { if (use_exact && done + take_n != n_total) xcs[lane] = xcode; }      /* (own lane's word only: no fence) */
             tail = (tail + take_n) & (kDenseRing - 1u);
             pend += take_n;
             if (TALLY) { q_cands += take_n; }
@@ -871,7 +960,7 @@ __device__ __forceinline__ void xgm_dense_unit(const xgm_seg_dev& seg, const xgm
     }
 
     /* ---- unit epilogue ---- */
-    dense_topk_sort(tk_w, tk_d, lane);
+    dense_topk_sort(tk_w, tk_d, PHRASE ? lane : dense_sort_lane(lane));
     for (int sh = 32; sh > 0; sh >>= 1) matches += (uint32_t)__shfl_xor((int)matches, sh);
     if (PHRASE) { for (int sh = 32; sh > 0; sh >>= 1) n_tested += (uint32_t)__shfl_xor((int)n_tested, sh); }
     if (PHRASE && TALLY) { for (int sh = 32; sh > 0; sh >>= 1) cn_pos += (unsigned long long)__shfl_xor((long long)cn_pos, sh); }
@@ -900,5 +989,5 @@ __device__ __forceinline__ void xgm_dense_unit(const xgm_seg_dev& seg, const xgm
         xgm_store_hdr(through, &ghdr_out[wk.slot], h);
     }
     if (through) xgm_unit_arrive<false>(*fuse, wk.qi, k, (uint32_t)__popc(q.score_mask), tk_w, tk_d, nullptr, kDenseCap, cand_out, ghdr_out, k_stride, lane,
-                           [&]() { dense_topk_sort(tk_w, tk_d, lane); });
+                           [&]() { dense_topk_sort(tk_w, tk_d, PHRASE ? lane : dense_sort_lane(lane)); });
 }

@@ -99,6 +99,7 @@ struct xgm_index {
     void* d_dense_dir = nullptr;
     void* d_dense_data = nullptr;
     void* d_dense_p2 = nullptr;        /* xgm_seg_dev::dense_p2 */
+    void* d_dense_wdf0 = nullptr;      /* xgm_seg_dev::dense_wdf0 */
     void* d_doclen_narrow = nullptr;   /* xgm_seg_dev::doclen_narrow */
     void* d_flat_off = nullptr;        /* flat posting arrays of the terms without containers (xgm_seg_dev::flat_*) */
     void* d_flat_did = nullptr;

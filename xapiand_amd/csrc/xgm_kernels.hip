@@ -625,9 +625,10 @@ __host__ __device__ inline size_t andw_wave_bytes(uint32_t W, uint32_t T, uint32
     off += phrase ? (size_t)T * kPosFast * 64 * 2 : 0;         /* lpos: the round's positions, u16 [T][kPosFast][64 lanes] */
     off += sided ? (size_t)cap : 0;                            /* tk_m: weighted subqueries matched, per top-k entry */
     /* the bodies for all-container / long-tail-led queries (xgm_dense_unit, xgm_flat_unit) run out of the first bytes of the same slice:
-     * top-k 1.5 KiB + offsets 0.5 KiB + the dense body's ring 1 KiB + the wdf != 1 summaries 1 KiB (positional: no summaries; + survivor queue
-     * <= 4 KiB + T x 2 KiB of staged positions) — static_asserts below.  The queue path's own tables are above 6 KiB for every launch. */
-    const size_t body = phrase ? 6144 + (size_t)T * 2048 : 4096;
+     * top-k 1.5 KiB + offsets 0.5 KiB + the dense body's ring 1 KiB + the wdf != 1 summaries 1 KiB + the lanes' packed plane bits 0.5 KiB (positional:
+     * neither; + survivor queue <= 4 KiB + T x 2 KiB of staged positions) — static_asserts below.  The queue path's own tables are above 6 KiB for every
+     * launch: stage + bitmap + rankw + c_slot alone are 3 136 bytes, the top-k buffer (cap >= 128) 1 536 more — no launch's slice comes from this reserve. */
+    const size_t body = phrase ? 6144 + (size_t)T * 2048 : 4608;
     if (off < body) off = body;
     return (off + 15) & ~(size_t)15;
 }
@@ -682,7 +683,8 @@ __device__ void wave_topk_sort(uint64_t* w_, uint32_t* d_, uint32_t cap, uint32_
 #include "xgm_unit_finish.h"
 #include "xgm_dense_body.inc"
 #include "xgm_flat_body.inc"
-static_assert(dense_wave_bytes(false) <= 4096 && flat_wave_bytes(false, 0) <= 4096, "andw_wave_bytes reserves 4 KiB for the plain bodies");
+static_assert(dense_wave_bytes(false) <= 4608 && flat_wave_bytes(false, 0) <= 4608, "andw_wave_bytes reserves 4.5 KiB for the plain bodies");
+static_assert((size_t)kStageWords * 4 + 128 * 4 + 256 * 2 + kAndwCandPlain * 2 + 128 * 12 >= 4608, "the queue path's tables exceed the plain bodies' reserve: the reserve sets no launch's slice");
 static_assert(dense_wave_bytes(true, 4) <= 6144 + 4 * 2048 && flat_wave_bytes(true, 4) <= 6144 + 4 * 2048 &&
               dense_wave_bytes(true, 2) <= 6144 + 2 * 2048 && flat_wave_bytes(true, 2) <= 6144 + 2 * 2048,
               "andw_wave_bytes reserves 6 KiB + T x 2 KiB for the positional bodies");

@@ -123,6 +123,11 @@ typedef struct {
      * of the bitmaps, a bit screen) and finds the bit clear has its wdf without a probe.  NULL: none. */
     const unsigned long long* dense_p2;
     uint32_t bit_screen;            /* xgm_flat_unit asks the screen term's bitmap (a sector of 512 documents) for membership instead of its wdf bytes (64) */
+    uint32_t exact_wdf;             /* xgm_dense_unit, stripes crowded with matches: wdf = 1 per document from the bits2 planes instead of the 128-slot summary */
+    /* One word per dense term (built with the containers): non-zero iff the term holds a posting of wdf 0 (a boolean posting: its byte reads 1).  A clear
+     * bits2 bit says wdf 0 or 1; only for a term WITHOUT such a posting does it say wdf = 1.  NULL: none, exact_wdf is then 0. */
+    const uint32_t* dense_wdf0;
+    unsigned long long reserved_;   /* (the view stays a multiple of 16 bytes: the kernels' arguments behind it keep their alignment) */
 } xgm_seg_dev;
 
 #define XGM_DENSE_MIN_AVG 32u          /* postings per stripe (on average) that make a term dense     */
