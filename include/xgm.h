@@ -633,6 +633,33 @@ int xgm_search_range(xgm_index*, const xgm_filter*, const xgm_sort_spec* sort /*
                      xgm_hit* hits, uint32_t* hit_ord /* may be NULL */, xgm_result_hdr* hdr,
                      int32_t spy_slot /* < 0 = none */, uint32_t* counts, uint32_t n_counts);
 
+/* The pair spy: for the documents of a filter, every distinct (ordinal in slot_a's plain column, ordinal in slot_b's plain column) with the
+ * number of documents carrying it — what an aggregation over TWO fields is made of (`_values` / `_histogram` / `_range` on one field with a
+ * metric sub-aggregation — `_avg`, `_sum`, `_min`, `_max`, `_stats` — on another), as the one-slot spy's counters are for one field: the caller
+ * shows its aggregation tree ONE document carrying the pair's two values and merges the result `count` times.
+ * Ordinal 0 (no value) is an ordinal like any other: the consumer decides what a bucket without a value means.  pairs[0 .. *n_pairs) are
+ * sorted ascending by (ord_a, ord_b), whichever path ran; their counts sum to the filter's n_docs; reserved is 0.  slot_a == slot_b is
+ * allowed and gives only diagonal pairs.  *n_pairs is always set on XGM_OK: when it exceeds cap nothing is written and it tells the room
+ * needed (xgm_search_all's convention; min(n_docs, (nA + 1)(nB + 1)) always suffices, nA / nB = the columns' distinct values).  A filter that
+ * lets nothing through gives *n_pairs = 0 without a launch.  A document whose ordinal exceeds its column's n_distinct is skipped, as the
+ * one-slot spy skips it.
+ * Two paths, chosen by P = (nA + 1)(nB + 1): up to 2^22 pairs one counter each (in LDS up to 8192), beyond that an open-addressing table
+ * of twice the pairs there can be, whose records the HOST sorts after the copy back — linear in the distinct pairs, as the consumer is.
+ * XGM_E_INVALID: a null idx / flt / n_pairs, null pairs with cap > 0, a filter built for another index or lastdocid; XGM_E_NO_DEVICE: an index
+ * without a device; XGM_UNSUPPORTED: a slot without a plain column, a column with n_distinct == 0xFFFFFFFF (the table's empty marker would be
+ * a pair), a table of more than 2^31 slots; XGM_E_NOMEM: no device memory for the counters, the table or the records.  Safe from any number
+ * of threads on one index and one filter: the filter and the columns are only read.
+ * NOT offered: pairs over a text query's match; list columns and per-element pairs; more than two slots; a page in the same call (call
+ * xgm_search_range beside this one).
+ * Replaces: the spy's operator() per document (api/matchspy.cc:307-313) under an AggregationMatchSpy tree of two fields
+ * (reference src/aggregations/aggregations.cc), called from the matcher's loop (matcher/matcher.cc:519-527). */
+typedef struct { uint32_t ord_a, ord_b, count, reserved; } xgm_pair_count;      /* 16 bytes */
+int xgm_filter_count_pairs(xgm_index*, const xgm_filter*, uint32_t slot_a, uint32_t slot_b,
+                           xgm_pair_count* pairs, uint64_t cap, uint64_t* n_pairs);
+/* Diagnostics: out4 = {the path of this THREAD's last xgm_filter_count_pairs that launched (1 counters in LDS, 2 counters by global atomics,
+ * 3 table; 0 none yet), its counters or table slots, its distinct pairs, the nanoseconds its host sort took}. */
+int xgm_debug_pairs_info(uint64_t* out4);
+
 /* EVERY matching document of a planned query — no page, no pruning — in ASCENDING DOCID order, each with its weight and the number
  * of weighted leaves matching it: the sequence the reference's matcher loop is shown by its posting-list tree (Matcher::get_local_mset,
  * matcher/matcher.cc:482-536) before ProtoMSet, the collapser, the spies or a cut-off look at it.  The plan's first / maxitems /

@@ -113,7 +113,11 @@ class ResultHdr(C.Structure):
                 ("max_attained", C.c_double), ("max_possible", C.c_double)]
 
 
-assert C.sizeof(Hit) == 16 and C.sizeof(ResultHdr) == 32
+class PairCount(C.Structure):
+    _fields_ = [("ord_a", C.c_uint32), ("ord_b", C.c_uint32), ("count", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(Hit) == 16 and C.sizeof(ResultHdr) == 32 and C.sizeof(PairCount) == 16
 
 # every symbol include/xgm.h declares: (name, restype, argtypes)
 _P = C.POINTER
@@ -144,6 +148,8 @@ _API = [
     ("xgm_search_filtered_batch", C.c_int, [C.c_void_p, _P(Query), C.c_uint32, C.c_void_p, _P(SortSpec), C.c_uint32, _P(Hit), _P(C.c_uint32), _P(ResultHdr),
                                    C.c_int32, _P(C.c_uint32), C.c_uint32]),
     ("xgm_search_range", C.c_int, [C.c_void_p, C.c_void_p, _P(SortSpec), C.c_uint32, _P(Hit), _P(C.c_uint32), _P(ResultHdr), C.c_int32, _P(C.c_uint32), C.c_uint32]),
+    ("xgm_filter_count_pairs", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, _P(PairCount), C.c_uint64, _P(C.c_uint64)]),
+    ("xgm_debug_pairs_info", C.c_int, [_P(C.c_uint64)]),
     ("xgm_segment_refresh_from_glass", C.c_int, [C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_char_p]),
     ("xgm_glass_export_raw", C.c_int, [C.c_char_p, C.c_char_p]),
     ("xgm_glass_info", C.c_int, [C.c_char_p, _P(C.c_uint64), _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint64)]),

@@ -127,3 +127,5 @@ int xgm_all_order_pack(void* tmp, uint32_t lastdocid, const unsigned long long* 
 
 /* the other selection over one bit per document: a value-range filter's bitmap as the whole query (xgm_search_range) */
 #include "xgm_range.h"
+/* ... and the passing documents counted per pair of ordinals in two columns (xgm_filter_count_pairs) */
+#include "xgm_pairs.h"

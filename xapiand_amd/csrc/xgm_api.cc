@@ -2334,6 +2334,117 @@ extern "C" int xgm_search_range(xgm_index* idx, const xgm_filter* flt, const xgm
     return XGM_OK;
 }
 
+/* ---- a filter's documents counted per pair of ordinals (include/xgm.h: xgm_filter_count_pairs) ---------------------------------------
+ * The kernels of xgm_pairs.h over the filter's bitmap and two columns.  The counters or the table live in the scratch's d_all — a table for a
+ * 10 M-document filter takes 400 MB —, the records right behind them in the same buffer, sized by what the caller has room for (160 MB more for
+ * 10 M pairs): the kAllKeepBytes rule above trims such a buffer from all but one pooled scratch, and no other buffer of the scratch grows with
+ * the size of the answer.  One launch sequence on the scratch's stream, then the pair count (8 bytes) and, when they fit the caller's room, the
+ * records through the pinned buffer in pieces.  The table's records arrive in slot order: sorted here by key. */
+constexpr uint64_t kPairDenseMax = 1ull << 22;                     /* counters (16 MB) up to which every possible pair gets one */
+constexpr size_t kPairCopyBytes = (size_t)4 << 20;                 /* the piece of pinned memory the records travel through */
+/* XGM_PAIRS_DENSE_MAX (diagnostic): overrides the threshold between counters and table; read once per process */
+static uint64_t pairs_dense_max() {
+    static const uint64_t v = [] {
+        const char* e = getenv("XGM_PAIRS_DENSE_MAX");
+        if (!e || !*e) return kPairDenseMax;
+        const long long x = atoll(e);
+        return (uint64_t)(x < 0 ? 0 : x > (1ll << 28) ? (1ll << 28) : x);
+    }();
+    return v;
+}
+static thread_local uint64_t t_pairs_info[4];
+extern "C" int xgm_debug_pairs_info(uint64_t* out4) { if (!out4) return -1; memcpy(out4, t_pairs_info, sizeof t_pairs_info); return 0; }
+
+extern "C" int xgm_filter_count_pairs(xgm_index* idx, const xgm_filter* flt, uint32_t slot_a, uint32_t slot_b, xgm_pair_count* pairs, uint64_t cap, uint64_t* n_pairs) {
+    if (!idx || !flt || !n_pairs || (!pairs && cap > 0)) return xgm_set_error(XGM_E_INVALID, "null argument");
+    *n_pairs = 0;
+    if (idx->device == XGM_DEVICE_NONE) return xgm_set_error(XGM_E_NO_DEVICE, "index opened without a device");
+    if (int frc = filter_usable(idx, flt)) return frc;
+    xgm_pairs_launch L = {};
+    {
+        std::lock_guard<std::mutex> lk(idx->columns_mu);
+        auto ia = idx->columns.find(slot_a), ib = idx->columns.find(slot_b);
+        if (ia == idx->columns.end() || ib == idx->columns.end())
+            return xgm_set_error(XGM_UNSUPPORTED, "pair counts: slot %u has no plain column attached", ia == idx->columns.end() ? slot_a : slot_b);
+        if (ia->second.second == 0xFFFFFFFFu || ib->second.second == 0xFFFFFFFFu)                             /* (the table's empty marker would be a pair) */
+            return xgm_set_error(XGM_UNSUPPORTED, "pair counts: the column of slot %u has n_distinct 0xFFFFFFFF", ia->second.second == 0xFFFFFFFFu ? slot_a : slot_b);
+        L.ord_a = (const uint32_t*)ia->second.first; L.n_a = ia->second.second;
+        L.ord_b = (const uint32_t*)ib->second.first; L.n_b = ib->second.second;
+    }
+    if (flt->n_docs == 0) return XGM_OK;                           /* nothing passes: no pair, no launch */
+    const uint64_t P = ((uint64_t)L.n_a + 1u) * ((uint64_t)L.n_b + 1u);          /* < 2^64: both factors are below 2^32 */
+    const uint64_t most = std::min<uint64_t>(flt->n_docs, P);      /* distinct pairs there can be */
+    L.sparse = P > pairs_dense_max();
+    L.n_slots = P;
+    if (L.sparse) {
+        L.n_slots = 1024;
+        while (L.n_slots < 2 * most) L.n_slots <<= 1;              /* most <= 2^32: no overflow */
+    }
+    if (L.n_slots > (1ull << 31))
+        return xgm_set_error(XGM_UNSUPPORTED, "pair counts: %llu documents over %llu possible pairs need a table of more than 2^31 slots", (unsigned long long)flt->n_docs, (unsigned long long)P);
+    int rc = use_device(idx->device);
+    if (rc) return rc;
+    L.bits = flt->d_bits;
+    L.n_tiles = flt->n_words_padded / XGM_FILTER_PAD_WORDS;
+    L.lastdocid = flt->lastdocid;
+    L.n_out = (uint32_t)std::min<uint64_t>(cap, most);
+    const xgm_pairs_layout y = xgm_pairs_work_layout(L.n_slots, L.sparse);
+    XgmScratch* sc;
+    if ((rc = scratch_acquire(idx, &sc))) return rc;
+    ScratchRelease release_{idx, sc};
+    auto room = [](unsigned char** p, size_t* have, size_t need) -> int {          /* grow(), with an allocation failure told apart */
+        if (need <= *have) return XGM_OK;
+        if (*p) HIP_TRY(hipFree(*p));
+        *p = nullptr; *have = 0;
+        const size_t n = need <= kAllKeepBytes ? need + need / 2 : need;         /* headroom where it is cheap: hipFree synchronises the device */
+        const hipError_t e = hipMalloc((void**)p, n);
+        if ((int)e == 2 /* hipErrorOutOfMemory */) { (void)hipGetLastError(); return xgm_set_error(XGM_E_NOMEM, "pair counts: out of device memory (%zu bytes)", n); }
+        if (e != hipSuccess) return xgm_launch_error("hipMalloc", (int)e, hipGetErrorString(e));
+        *have = n;
+        return XGM_OK;
+    };
+    if ((rc = room(&sc->d_all, &sc->cap_all, y.total + std::max<size_t>((size_t)L.n_out * sizeof(xgm_pair_count), 256)))) return rc;          /* (y.total is a multiple of 256) */
+    if ((rc = grow_pinned(&sc->h_sorted, &sc->cap_hsorted, std::min<size_t>(kPairCopyBytes, std::max<size_t>((size_t)L.n_out * sizeof(xgm_pair_count), 256))))) return rc;
+    L.work = sc->d_all;
+    L.out = (xgm_pair_count*)(sc->d_all + y.total);
+    if (idx->profiling) {
+        std::lock_guard<std::mutex> lk(idx->scratch_mu);
+        if (idx->prof_used == idx->prof_events.size()) {
+            hipEvent_t a, b;
+            HIP_TRY(hipEventCreate(&a));
+            HIP_TRY(hipEventCreate(&b));
+            idx->prof_events.push_back({a, b});
+        }
+        L.ev_start = (hipEvent_t)idx->prof_events[idx->prof_used].first;
+        L.ev_stop = (hipEvent_t)idx->prof_events[idx->prof_used].second;
+        ++idx->prof_used;
+    }
+    idx->last_kernel = "xgm_pairs_tally_kernel";
+    if ((rc = xgm_launch_pairs(L, sc->stream))) return rc;
+    uint32_t* hw = (uint32_t*)sc->h_sorted;                        /* [0] distinct pairs, [1] the error word */
+    HIP_TRY(hipMemcpyAsync(hw, sc->d_all + y.o_hdr, 8, hipMemcpyDeviceToHost, sc->stream));
+    HIP_TRY(hipStreamSynchronize(sc->stream));
+    const uint64_t n = hw[0];
+    if (hw[1] != 0 || n > most) return xgm_set_error(XGM_E_DEVICE, "pair counts: %llu pairs where at most %llu can be, %u insertions found the table full", (unsigned long long)n, (unsigned long long)most, hw[1]);
+    *n_pairs = n;
+    t_pairs_info[0] = L.sparse ? 3 : L.n_slots <= 8192 ? 1 : 2;    /* (8192: kRangeSpyLds of xgm_range.h) */
+    t_pairs_info[1] = L.n_slots; t_pairs_info[2] = n; t_pairs_info[3] = 0;
+    if (n > cap) return XGM_OK;                                    /* nothing written: *n_pairs tells the room needed */
+    const size_t per = std::min<size_t>(kPairCopyBytes, sc->cap_hsorted) / sizeof(xgm_pair_count);
+    for (size_t at = 0; at < n; at += per) {
+        const size_t m = std::min<size_t>(per, (size_t)n - at);
+        HIP_TRY(hipMemcpyAsync(sc->h_sorted, L.out + at, m * sizeof(xgm_pair_count), hipMemcpyDeviceToHost, sc->stream));
+        HIP_TRY(hipStreamSynchronize(sc->stream));
+        memcpy(pairs + at, sc->h_sorted, m * sizeof(xgm_pair_count));
+    }
+    if (L.sparse) {
+        const uint64_t t0 = now_ns();
+        std::sort(pairs, pairs + n, [](const xgm_pair_count& x, const xgm_pair_count& z) { return x.ord_a != z.ord_a ? x.ord_a < z.ord_a : x.ord_b < z.ord_b; });
+        t_pairs_info[3] = now_ns() - t0;
+    }
+    return XGM_OK;
+}
+
 /* ---- every match of a query, in docid order (include/xgm.h: xgm_search_all) -------------------------------------------------
  * The workgroup kernel (every query shape; it decodes the posting blocks of each stripe: K1 at full size) weighs every matching
  * document anyway when it runs under a sort; here it also appends each to one list (a wave-aggregated atomic per round), which

@@ -86,6 +86,25 @@ struct xgm_range_launch {
 struct xgm_range_layout { size_t o_state, o_ghist, o_counts, o_hdr, o_hits, o_ords, o_pairs, o_tiles, b_tiles, total; };
 xgm_range_layout xgm_range_work_layout(uint32_t n_tiles, uint32_t k, uint32_t n_counts);
 int xgm_launch_range(const xgm_range_launch& L, hipStream_t stream);
+/* a filter's passing documents counted per pair of ordinals in two plain columns (xgm_pairs.h, xgm_filter_count_pairs).  Dense (sparse false):
+ * n_slots = (n_a + 1)(n_b + 1) counters, the records come out in (a, b) order; sparse: n_slots = a power of two >= twice the distinct pairs there
+ * can be, the records come out in slot order.  work = xgm_pairs_work_layout(...).total device bytes, 256-byte aligned; afterwards its first two
+ * words hold the number of distinct pairs and an error word (non-zero: the table was full), out [0 .. min(n_out, pairs)) the records. */
+struct xgm_pairs_launch {
+    const uint32_t* bits;             /* device, n_tiles * XGM_FILTER_PAD_WORDS words (xgm_launch_filter_mark) */
+    uint32_t n_tiles, lastdocid;
+    const uint32_t* ord_a, *ord_b;    /* device columns [lastdocid + 1]; may be the same */
+    uint32_t n_a, n_b;                /* their n_distinct, below 0xFFFFFFFF */
+    uint64_t n_slots;                 /* <= 2^31 */
+    bool sparse;
+    unsigned char* work;
+    xgm_pair_count* out;              /* device, [n_out]; n_out 0: count only */
+    uint32_t n_out;
+    hipEvent_t ev_start = nullptr, ev_stop = nullptr;      /* recorded around the kernels when set */
+};
+struct xgm_pairs_layout { size_t o_hdr, o_counters, o_keys, o_chunk_cnt, o_chunk_off, total; uint32_t n_chunks; };
+xgm_pairs_layout xgm_pairs_work_layout(uint64_t n_slots, bool sparse);
+int xgm_launch_pairs(const xgm_pairs_launch& L, hipStream_t stream);
 /* all_keys != NULL (xgm_search_all): every matching document is also appended, in no particular order, to all_keys / all_vals
  * (docid << 32 | weighted leaves matched, weight bits) at the position the zeroed counter *all_count hands out; entries beyond all_cap
  * are counted, not written.  xgm_all_order_pack (xgm_all.hip) restores docid order: tmp = xgm_all_order_bytes(lastdocid) device bytes. */

@@ -581,6 +581,25 @@ def search_range(db, flt, k, sort_by=None, slot=0, reverse=False, spy=None):
     return [(hits[i].docid, hits[i].weight, hits[i].subqs_matched, ords[i]) for i in range(hdr.n_hits)], hdr, (list(counts) if nc else None)
 
 
+def count_pairs(db, flt, slot_a, slot_b):
+    """xgm_filter_count_pairs: the filter's documents counted per (ordinal in slot_a, ordinal in slot_b) — what an aggregation over two fields is
+    made of.  Asks for the room needed first (cap 0), then with it.  Returns [(ord_a, ord_b, count)] ascending by (ord_a, ord_b); the counts sum to
+    flt.n_docs; ordinal 0 = no value."""
+    l = _lib.lib()
+    n = C.c_uint64()
+    _lib.check(l.xgm_filter_count_pairs(db._h, flt._h, slot_a, slot_b, None, 0, C.byref(n)))
+    if n.value == 0:
+        return []
+    cap = n.value
+    pairs = (_lib.PairCount * cap)()
+    _lib.check(l.xgm_filter_count_pairs(db._h, flt._h, slot_a, slot_b, pairs, cap, C.byref(n)))
+    if n.value != cap:
+        raise RuntimeError("xgm_filter_count_pairs: %d pairs, then %d" % (cap, n.value))
+    import numpy as np
+    a = np.frombuffer(pairs, dtype=np.uint32).reshape(-1, 4)
+    return list(zip(a[:, 0].tolist(), a[:, 1].tolist(), a[:, 2].tolist()))
+
+
 def search_collapsed(db, planned, collapse_slot, collapse_max, sort_by=None, slot=0, reverse=False):
     """xgm_search_collapsed: set_collapse_key(collapse_slot, collapse_max), ranked by relevance (sort_by None) or under a value sort.
     Returns ([(docid, weight, subqs, sort ordinal, collapse ordinal, collapse count)], hdr, collapsed lower bound)."""
