@@ -1318,6 +1318,23 @@ void xgo_index_set_synthetic_values(void* ixv, uint64_t seed, uint32_t n_shards,
     }
 }
 
+/* One value slot from the caller: document d's value is bytes[offsets[d] .. offsets[d + 1]), d = 0 .. lastdocid (offsets has
+ * lastdocid + 2 entries; an empty string = no value; docid 0 has none).  At most 7 bytes each: the searches hand keys out with a stride
+ * of 8.  The other slots stay as they are; slots below `slot` that do not exist yet are made, empty. */
+int xgo_index_set_values(void* ixv, uint32_t slot, const uint64_t* offsets, const char* bytes) {
+    Index* ix = (Index*)ixv;
+    if (!ix || !offsets || slot >= 64u || offsets[0] != offsets[1]) return -1;
+    for (uint32_t d = 0; d <= ix->lastdocid; ++d)
+        if (offsets[d + 1] < offsets[d] || offsets[d + 1] - offsets[d] > 7u) return -1;
+    if (ix->values.size() <= slot) ix->values.resize(slot + 1u);
+    std::vector<std::string>& value = ix->values[slot];
+    value.assign(ix->lastdocid + 1, std::string());
+    for (uint32_t d = 1; d <= ix->lastdocid; ++d)
+        if (offsets[d + 1] > offsets[d]) { if (!bytes) return -1; value[d].assign(bytes + offsets[d], (size_t)(offsets[d + 1] - offsets[d])); }
+    for (std::vector<std::string>& other : ix->values) if (other.size() != value.size()) other.assign(value.size(), std::string());
+    return 0;
+}
+
 /* One value slot of the index as the column file of include/xgm.h (xgm_glass_export_column writes the same from glass): the
  * documents' ordinals among the slot's distinct values, then the values.  For device tests that have no glass database. */
 int xgo_write_value_column(void* ixv, uint32_t slot, const char* path) {

@@ -524,6 +524,28 @@ class ManualCorpus(Corpus):
     def terms(self):
         return list(self._term_bytes)
 
+    def set_values(self, slot, values):
+        """One value slot of the oracle's index from {docid: bytes} (at most 7 bytes each: the oracle hands keys out with a stride of 8; a docid
+        left out, or b"", has no value).  After it oracle_search_sorted / oracle_spy work on this corpus, and write_value_column writes the slot."""
+        last = self.v.lastdocid
+        assert all(1 <= d <= last and len(v) <= 7 for d, v in values.items())
+        off = np.zeros(last + 2, dtype=np.uint64)
+        off[1:] = np.cumsum([len(values.get(d, b"")) for d in range(last + 1)], dtype=np.uint64)
+        blob = b"".join(values.get(d, b"") for d in range(last + 1))
+        ol = olib()
+        ol.xgo_index_set_values.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.c_char_p]
+        assert ol.xgo_index_set_values(self.oracle_index(), slot, off.ctypes.data_as(C.POINTER(C.c_uint64)), blob) == 0
+        self._values_set = True
+
+
+def write_value_column(corpus, slot, path):
+    """The oracle's value slot as a column file (oracle/xgm_oracle.cc::xgo_write_value_column); the slots must be set."""
+    assert getattr(corpus, "_values_set", False)
+    ol = olib()
+    ol.xgo_write_value_column.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p]
+    assert ol.xgo_write_value_column(corpus.oracle_index(), slot, path.encode()) == 0
+    return path
+
 
 def coloc_postings(seed=0xC010C, n_docs=600):
     """Documents whose indexer puts SEVERAL TERMS AT ONE POSITION (a word's prefixed and unprefixed forms, synonyms): what engages the
