@@ -585,6 +585,43 @@ int xgm_filter_build(xgm_index*, const xgm_value_range* ranges, uint32_t n_range
 int xgm_filter_read(const xgm_filter*, uint32_t* words, uint32_t n_words);
 void xgm_filter_free(xgm_filter*);
 
+/* The second producer of a filter: the MATCH SET of a planned, non-positional query, one bit per document — exactly the docids
+ * xgm_search_all lists for the same plan, *n_docs (may be NULL) = its *n_matches.  Weights, first / maxitems / check_at_least and replay are
+ * ignored: membership is read straight off the postings (a dense term's container bitmaps, a long-tail term's flat docid array, the blocks of
+ * any other term), by docid range, and the plan's boolean structure is evaluated on words of 32 documents; nothing is weighed, listed or
+ * ranked, and 8 bytes come back.  The result is an ordinary xgm_filter with xgm_filter_build's contract: padded, every word written, bit 0 and
+ * the bits beyond lastdocid clear, immutable, bound to the index's lastdocid, usable from any thread by xgm_search_filtered*,
+ * xgm_search_range, xgm_filter_count_pairs and xgm_filter_combine.  Synchronous; safe from any number of threads on one index.
+ * Accepted: every non-positional shape xgm_plan_query produces — a term; XGM_OP_AND, _OR, _AND_NOT, _FILTER; _AND_MAYBE (the set is the left
+ * side's); XGM_OP_TREE with synonym / wildcard groups (a group is the union of its members; nodes AND, OR, ANDNOT, and MAYBE = its left
+ * operand); XGM_OP_PHRASE / _NEAR with phrase_active == 0 (an AND).  A leaf absent from the shard (term_id == UINT32_MAX) is the empty set.
+ * What it is for.  (1) A boolean restriction — keyword or boolean fields under a DSL `_filter`, `Query(OP_SCALE_WEIGHT, q, 0)` — beside or
+ * instead of a text query.  (2) Xapiand's `_range` as the whole request: MultipleValueRange::getQuery builds OP_FILTER(MultipleValue*,
+ * OR of accuracy terms) (reference src/multivalue/range.cc:100-126); the accuracy-term side is this call on the planned OR, the posting source
+ * a XGM_RANGE_LIST* (or plain) clause filter, the two joined by xgm_filter_combine(XGM_FILTER_AND) and answered by xgm_search_range.
+ * xgm_search_range over such a filter returns weights +0.0 in docid / value order: the reference's answer when every weight of the tree is 0
+ * (matcher/matcher.cc:415-430).  MultipleValue*::get_weight's constant 1.0 is the hook's to add or to decline.
+ * XGM_E_INVALID: a null idx / plan / out, a plan that is not well formed (a term id beyond the dictionary, masks or tree operands out of
+ * range); XGM_E_NO_DEVICE: an index without a device; XGM_UNSUPPORTED: an ACTIVE positional plan (PHRASE / NEAR with phrase_active), a tree
+ * that reuses a node so often that its expansion exceeds the kernel's program.
+ * NOT offered: positional plans; a complement or Query::MatchAll (which documents EXIST is another question); several plans in one launch;
+ * shards; xgm_mset_bounds* of a search under such a filter.  The matcher hook does not lower to this call yet.
+ * Replaces: OP_FILTER's boolean right-hand side and Query(OP_SCALE_WEIGHT, q, 0) as the matcher walks them per candidate
+ * (matcher/matcher.cc:482-536); for `_range`, the accuracy-term side of OP_FILTER(MultipleValue*, terms). */
+int xgm_filter_build_query(xgm_index*, const xgm_query* plan, xgm_filter** out, uint64_t* n_docs /* may be NULL */);
+
+/* A new filter from two filters of the same index and lastdocid: a & b, a | b or a & ~b, word by word on the device; a and b stay as they are
+ * (a == b is allowed), *n_docs (may be NULL) = the documents of the result.  DSL `_and` / `_or` / `_not` BETWEEN restrictions: two ranges
+ * OR-ed, a range minus a term, a clause filter AND a query filter.  Synchronous; safe from any number of threads.
+ * XGM_E_INVALID: a null idx / a / b / out, an op outside 1 .. 3, a filter of another device or lastdocid; XGM_E_NO_DEVICE: an index without
+ * a device.
+ * NOT offered: a complement (NOT b alone) and Query::MatchAll — AND_NOT needs a left side; more than two operands in one call.
+ * Replaces: MultiAndPostList / OrPostList / AndNotPostList over unweighted sub-trees under OP_FILTER (matcher/matcher.cc:482-536). */
+#define XGM_FILTER_AND     1u   /* a & b  */
+#define XGM_FILTER_OR      2u   /* a | b  */
+#define XGM_FILTER_AND_NOT 3u   /* a & ~b */
+int xgm_filter_combine(xgm_index*, uint32_t op, const xgm_filter* a, const xgm_filter* b, xgm_filter** out, uint64_t* n_docs /* may be NULL */);
+
 /* xgm_search_sorted / xgm_search_sorted_spy for Query(OP_FILTER, q, range_1 AND ... AND range_n): the documents of q that the filter lets
  * through, under the given sort (sort == NULL: by relevance), with a ValueCountMatchSpy on spy_slot when spy_slot >= 0 (counts / n_counts
  * as for xgm_search_sorted_spy; ignored otherwise).  Every query shape xgm_search_sorted takes.  hdr->matches_exact counts the filtered
@@ -649,8 +686,8 @@ int xgm_search_range(xgm_index*, const xgm_filter*, const xgm_sort_spec* sort /*
  * without a device; XGM_UNSUPPORTED: a slot without a plain column, a column with n_distinct == 0xFFFFFFFF (the table's empty marker would be
  * a pair), a table of more than 2^31 slots; XGM_E_NOMEM: no device memory for the counters, the table or the records.  Safe from any number
  * of threads on one index and one filter: the filter and the columns are only read.
- * NOT offered: pairs over a text query's match; list columns and per-element pairs; more than two slots; a page in the same call (call
- * xgm_search_range beside this one).
+ * Pairs over a text query's match: count them over the query's filter (xgm_filter_build_query), alone or combined with a range filter.
+ * NOT offered: list columns and per-element pairs; more than two slots; a page in the same call (call xgm_search_range beside this one).
  * Replaces: the spy's operator() per document (api/matchspy.cc:307-313) under an AggregationMatchSpy tree of two fields
  * (reference src/aggregations/aggregations.cc), called from the matcher's loop (matcher/matcher.cc:519-527). */
 typedef struct { uint32_t ord_a, ord_b, count, reserved; } xgm_pair_count;      /* 16 bytes */

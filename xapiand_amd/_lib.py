@@ -102,6 +102,7 @@ XGM_RANGE_VALUE, XGM_RANGE_LIST, XGM_RANGE_LIST_GE, XGM_RANGE_LIST_LE = 0, 1, 2,
 XGM_MAX_RANGES = 4
 XGM_ORD_MAX = 0xFFFFFFFF
 XGM_RANGE_NO_END = 1
+XGM_FILTER_AND, XGM_FILTER_OR, XGM_FILTER_AND_NOT = 1, 2, 3          # xgm_filter_combine
 
 
 class Hit(C.Structure):
@@ -144,6 +145,8 @@ _API = [
     ("xgm_filter_build", C.c_int, [C.c_void_p, _P(ValueRange), C.c_uint32, _P(C.c_void_p), _P(C.c_uint64)]),
     ("xgm_filter_read", C.c_int, [C.c_void_p, _P(C.c_uint32), C.c_uint32]),
     ("xgm_filter_free", None, [C.c_void_p]),
+    ("xgm_filter_build_query", C.c_int, [C.c_void_p, _P(Query), _P(C.c_void_p), _P(C.c_uint64)]),
+    ("xgm_filter_combine", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, _P(C.c_void_p), _P(C.c_uint64)]),
     ("xgm_search_filtered", C.c_int, [C.c_void_p, _P(Query), C.c_void_p, _P(SortSpec), _P(Hit), _P(C.c_uint32), _P(ResultHdr), C.c_int32, _P(C.c_uint32), C.c_uint32]),
     ("xgm_search_filtered_batch", C.c_int, [C.c_void_p, _P(Query), C.c_uint32, C.c_void_p, _P(SortSpec), C.c_uint32, _P(Hit), _P(C.c_uint32), _P(ResultHdr),
                                    C.c_int32, _P(C.c_uint32), C.c_uint32]),

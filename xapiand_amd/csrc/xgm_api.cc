@@ -2243,6 +2243,167 @@ extern "C" void xgm_filter_free(xgm_filter* flt) {
     delete flt;
 }
 
+/* ---- filters from term queries; filter algebra (include/xgm.h: xgm_filter_build_query, xgm_filter_combine) --------------------------
+ * The plan's match predicate — the one to_dev_query hands the match kernels: req_mask / neg_mask for the flat operators, groups and binary
+ * nodes for a tree — compiled into the postfix program of xgm_filter_terms.h, which evaluates it on words of 32 documents. */
+
+namespace {
+struct FilterProgramBuilder {
+    const xgm_query* q;
+    xgm_filter_program* pg;
+    uint32_t used = 0;                         /* plan positions the program reads */
+    bool overflow = false;
+    uint8_t label[XGM_MAX_TERMS + XGM_MAX_TREE];
+    void emit(uint32_t op, uint32_t t = 0) {
+        if (pg->n_code == XGM_FQ_MAX_CODE) { overflow = true; return; }
+        pg->code[pg->n_code++] = (uint8_t)(op << 4 | t);
+        if (op <= XGM_FQ_ANDNOT_T) used |= 1u << t;
+    }
+    /* a group's only member, or -1 */
+    int single(uint32_t v) const {
+        if (v >= q->n_groups) return -1;
+        int only = -1;
+        for (uint32_t t = 0; t < q->n_terms; ++t) if (q->group_of[t] == v) { if (only >= 0) return -1; only = (int)t; }
+        return only;
+    }
+    /* stack values the evaluation of v needs (Sethi-Ullman): a group 1; a MAYBE its left side's; a node whose right side is one term its
+     * left side's; else the larger of the two, one more when they are equal — the deeper side is evaluated first */
+    void labels() {
+        for (uint32_t g = 0; g < q->n_groups; ++g) label[g] = 1;
+        for (uint32_t j = 0; j < q->tree_len; ++j) {
+            const uint8_t la = label[q->tree_a[j]], lb = label[q->tree_b[j]];
+            label[q->n_groups + j] = (q->tree_op[j] == XGM_N_MAYBE || single(q->tree_b[j]) >= 0) ? la : la == lb ? (uint8_t)(la + 1) : std::max(la, lb);
+        }
+    }
+    void value(uint32_t v) {
+        if (overflow) return;
+        if (v < q->n_groups) {                 /* the union of the group's members; a group without one (never planned) is empty: an absent leaf would say so */
+            bool first = true;
+            for (uint32_t t = 0; t < q->n_terms; ++t) if (q->group_of[t] == v) { emit(first ? XGM_FQ_PUSH : XGM_FQ_OR_T, t); first = false; }
+            if (first) overflow = true;
+            return;
+        }
+        const uint32_t j = v - q->n_groups, op = q->tree_op[j], a = q->tree_a[j], b = q->tree_b[j];
+        if (op == XGM_N_MAYBE) { value(a); return; }                       /* AndMaybePostList: the left side decides who matches */
+        const int t = single(b);
+        if (t >= 0) { value(a); emit(op == XGM_N_AND ? XGM_FQ_AND_T : op == XGM_N_OR ? XGM_FQ_OR_T : XGM_FQ_ANDNOT_T, (uint32_t)t); return; }
+        if (label[a] >= label[b]) { value(a); value(b); emit(op == XGM_N_AND ? XGM_FQ_AND : op == XGM_N_OR ? XGM_FQ_OR : XGM_FQ_ANDNOT); }
+        else { value(b); value(a); emit(op == XGM_N_AND ? XGM_FQ_AND : op == XGM_N_OR ? XGM_FQ_OR : XGM_FQ_RANDNOT); }
+    }
+};
+}  // namespace
+
+/* XGM_OK, XGM_E_INVALID (a plan the planner would not have produced) or XGM_UNSUPPORTED */
+static int filter_program_of(const xgm_index* idx, const xgm_query* q, xgm_filter_program* pg) {
+    memset(pg, 0, sizeof *pg);
+    if ((q->op == XGM_OP_PHRASE || q->op == XGM_OP_NEAR) && q->phrase_active) return XGM_UNSUPPORTED;
+    if (q->op < XGM_OP_AND || q->op > XGM_OP_TREE) return xgm_set_error(XGM_E_INVALID, "query filter: op %u", q->op);
+    if (q->n_terms == 0 || q->n_terms > XGM_MAX_TERMS) return xgm_set_error(XGM_E_INVALID, "query filter: %u terms", q->n_terms);
+    pg->n_terms = q->n_terms;
+    for (uint32_t t = 0; t < q->n_terms; ++t) {
+        pg->term_id[t] = q->terms[t].term_id;
+        if (pg->term_id[t] != UINT32_MAX && pg->term_id[t] >= idx->hdr.n_terms) return xgm_set_error(XGM_E_INVALID, "query filter: term id %u of %u", pg->term_id[t], idx->hdr.n_terms);
+    }
+    FilterProgramBuilder fb{q, pg};
+    if (q->op == XGM_OP_TREE) {
+        /* to_dev_query's checks of a tree, then the program in the builder's order */
+        if (q->n_groups == 0 || q->n_groups > XGM_MAX_TERMS || q->tree_len > XGM_MAX_TREE || q->tree_root >= q->n_groups + q->tree_len)
+            return xgm_set_error(XGM_E_INVALID, "query filter: malformed tree");
+        for (uint32_t t = 0; t < q->n_terms; ++t) if (q->group_of[t] >= q->n_groups) return xgm_set_error(XGM_E_INVALID, "query filter: malformed tree");
+        for (uint32_t j = 0; j < q->tree_len; ++j)
+            if (q->tree_a[j] >= q->n_groups + j || q->tree_b[j] >= q->n_groups + j || q->tree_op[j] < XGM_N_AND || q->tree_op[j] > XGM_N_MAYBE)
+                return xgm_set_error(XGM_E_INVALID, "query filter: malformed tree");
+        fb.labels();
+        if (fb.label[q->tree_root] > XGM_FQ_STACK) return XGM_UNSUPPORTED;
+        fb.value(q->tree_root);
+    } else if (q->op == XGM_OP_OR) {
+        for (uint32_t t = 0; t < q->n_terms; ++t) fb.emit(t ? XGM_FQ_OR_T : XGM_FQ_PUSH, t);
+    } else {
+        /* AND / FILTER / degraded PHRASE / NEAR: every term required; AND_NOT: and none of neg_mask; AND_MAYBE: the others decide nothing */
+        if (q->req_mask == 0 || (q->n_terms < 32u && (q->req_mask >> q->n_terms) != 0) || (q->req_mask & q->neg_mask) || (q->n_terms < 32u && (q->neg_mask >> q->n_terms) != 0))
+            return xgm_set_error(XGM_E_INVALID, "query filter: masks %x / %x of %u terms", q->req_mask, q->neg_mask, q->n_terms);
+        bool first = true;
+        for (uint32_t t = 0; t < q->n_terms; ++t) if ((q->req_mask >> t) & 1u) { fb.emit(first ? XGM_FQ_PUSH : XGM_FQ_AND_T, t); first = false; }
+        for (uint32_t t = 0; t < q->n_terms; ++t) if ((q->neg_mask >> t) & 1u) fb.emit(XGM_FQ_ANDNOT_T, t);
+    }
+    if (fb.overflow) return XGM_UNSUPPORTED;
+    for (uint32_t t = 0; t < q->n_terms; ++t) if (!((fb.used >> t) & 1u)) pg->term_id[t] = UINT32_MAX;     /* never read: no load */
+    return XGM_OK;
+}
+
+/* What xgm_filter_build does around its kernel, for the two producers below: a scratch of the pool, the counter, the bitmap, the event pair
+ * under xgm_index_set_profiling, one copy back, the filter.  launch(d_bits, n_padded, d_count, stream) enqueues the kernel. */
+template <class Launch>
+static int filter_produce(xgm_index* idx, const char* kernel_name, Launch&& launch, xgm_filter** out, uint64_t* n_docs) {
+    int rc = use_device(idx->device);
+    if (rc) return rc;
+    const uint64_t n_bits = (uint64_t)idx->hdr.lastdocid + 1u;
+    const uint32_t n_words = (uint32_t)((n_bits + 31u) / 32u);
+    const uint32_t n_padded = (uint32_t)(((uint64_t)n_words + XGM_FILTER_PAD_WORDS - 1u) / XGM_FILTER_PAD_WORDS * XGM_FILTER_PAD_WORDS);
+    XgmScratch* sc;
+    if ((rc = scratch_acquire(idx, &sc))) return rc;
+    ScratchRelease release_{idx, sc};
+    DeviceBuffers tmp;
+    unsigned long long* d_count = nullptr;
+    if ((rc = tmp.alloc((void**)&d_count, 8))) return rc;
+    uint32_t* d_bits = nullptr;
+    HIP_TRY(hipMalloc((void**)&d_bits, (size_t)n_padded * 4));
+    unsigned long long count = 0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;                             /* xgm_index_set_profiling: a pair around the kernel (tools/filter_query_time.py) */
+    if (idx->profiling) {
+        std::lock_guard<std::mutex> lk(idx->scratch_mu);
+        if (idx->prof_used == idx->prof_events.size()) {
+            hipEvent_t a = nullptr, b = nullptr;
+            if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { if (a) hipEventDestroy(a); hipFree(d_bits); return xgm_launch_error(kernel_name, 0, "hipEventCreate"); }
+            idx->prof_events.push_back({a, b});
+        }
+        ev0 = (hipEvent_t)idx->prof_events[idx->prof_used].first;
+        ev1 = (hipEvent_t)idx->prof_events[idx->prof_used].second;
+        ++idx->prof_used;
+    }
+    hipError_t e = hipMemsetAsync(d_count, 0, 8, sc->stream);
+    if (e == hipSuccess) {
+        if (ev0) hipEventRecord(ev0, sc->stream);
+        rc = launch(d_bits, n_padded, d_count, sc->stream);
+        if (ev1) hipEventRecord(ev1, sc->stream);
+        if (rc) { hipStreamSynchronize(sc->stream); hipFree(d_bits); return rc; }
+        if (ev0) idx->last_kernel = kernel_name;
+        e = hipMemcpyAsync(&count, d_count, 8, hipMemcpyDeviceToHost, sc->stream);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(sc->stream);
+    if (e != hipSuccess) { hipStreamSynchronize(sc->stream); hipFree(d_bits); return xgm_launch_error(kernel_name, (int)e, hipGetErrorString(e)); }
+    xgm_filter* flt = new xgm_filter();
+    flt->device = idx->device; flt->lastdocid = idx->hdr.lastdocid;
+    flt->n_words = n_words; flt->n_words_padded = n_padded;
+    flt->d_bits = d_bits; flt->n_docs = count;
+    if (n_docs) *n_docs = count;
+    *out = flt;
+    return XGM_OK;
+}
+
+extern "C" int xgm_filter_build_query(xgm_index* idx, const xgm_query* plan, xgm_filter** out, uint64_t* n_docs) {
+    if (!idx || !plan || !out) return xgm_set_error(XGM_E_INVALID, "null argument");
+    *out = nullptr;
+    if (idx->device == XGM_DEVICE_NONE) return xgm_set_error(XGM_E_NO_DEVICE, "index opened without a device");
+    xgm_filter_program pg;
+    if (int prc = filter_program_of(idx, plan, &pg)) return prc;
+    return filter_produce(idx, "xgm_filter_mark_query_kernel", [&](uint32_t* d_bits, uint32_t n_padded, unsigned long long* d_count, hipStream_t stream) {
+        return xgm_launch_filter_mark_query(idx->view, pg, n_padded, d_bits, d_count, stream);
+    }, out, n_docs);
+}
+
+extern "C" int xgm_filter_combine(xgm_index* idx, uint32_t op, const xgm_filter* a, const xgm_filter* b, xgm_filter** out, uint64_t* n_docs) {
+    if (!idx || !a || !b || !out) return xgm_set_error(XGM_E_INVALID, "null argument");
+    *out = nullptr;
+    if (idx->device == XGM_DEVICE_NONE) return xgm_set_error(XGM_E_NO_DEVICE, "index opened without a device");
+    if (op < XGM_FILTER_AND || op > XGM_FILTER_AND_NOT) return xgm_set_error(XGM_E_INVALID, "filter combine: op %u (1 .. 3)", op);
+    if (int frc = filter_usable(idx, a)) return frc;
+    if (int frc = filter_usable(idx, b)) return frc;
+    return filter_produce(idx, "xgm_filter_combine_kernel", [&](uint32_t* d_bits, uint32_t n_padded, unsigned long long* d_count, hipStream_t stream) {
+        return xgm_launch_filter_combine(a->d_bits, b->d_bits, op, n_padded, d_bits, d_count, stream);
+    }, out, n_docs);
+}
+
 extern "C" int xgm_search_filtered(xgm_index* idx, const xgm_query* q, const xgm_filter* flt, const xgm_sort_spec* sort, xgm_hit* hits, uint32_t* hit_ord,
                                    xgm_result_hdr* hdr, int32_t spy_slot, uint32_t* counts, uint32_t n_counts) {
     if (!flt) return xgm_set_error(XGM_E_INVALID, "null argument");

@@ -68,6 +68,32 @@ struct xgm_filter_clauses {
 /* a filter of XGM_RANGE_VALUE clauses alone launches xgm_filter_mark_kernel, any list kind among them xgm_filter_mark_lists_kernel */
 int xgm_launch_filter_mark(const xgm_filter_clauses& cl, uint32_t lastdocid, uint32_t n_words_padded, uint32_t* bits, unsigned long long* count,
                            hipStream_t stream);
+/* filters from term queries (xgm_filter_terms.h): the same bitmap, the same padding and the same count, for the match set of a planned
+ * non-positional query.  The plan's predicate travels by value as a postfix program over its leaves: a byte is (op << 4 | leaf).  The leaf ops
+ * work on the top of a stack of XGM_FQ_STACK values of the unit's words — PUSH the leaf's membership, or AND / OR / AND-NOT it into the top (a
+ * synonym group is PUSH + OR_T of its members, a chain of single terms never grows the stack) — the others pop r, pop l and push l & r, l | r,
+ * l & ~r or r & ~l (RANDNOT: the host evaluates the deeper operand first, which keeps any tree of XGM_MAX_TERMS leaves inside five values).
+ * A leaf whose term_id is UINT32_MAX — absent in the shard, or never referenced: the right side of a MAYBE — is the empty set and costs no load. */
+#define XGM_FQ_PUSH 0u
+#define XGM_FQ_AND_T 1u
+#define XGM_FQ_OR_T 2u
+#define XGM_FQ_ANDNOT_T 3u
+#define XGM_FQ_AND 4u
+#define XGM_FQ_OR 5u
+#define XGM_FQ_ANDNOT 6u
+#define XGM_FQ_RANDNOT 7u
+#define XGM_FQ_STACK 6u
+#define XGM_FQ_MAX_CODE 64u               /* >= XGM_MAX_TERMS leaf ops + XGM_MAX_TREE node ops */
+struct xgm_filter_program {
+    uint32_t n_terms, n_code;
+    uint32_t term_id[XGM_MAX_TERMS];
+    uint8_t code[XGM_FQ_MAX_CODE];
+};
+int xgm_launch_filter_mark_query(const xgm_seg_dev& seg, const xgm_filter_program& pg, uint32_t n_words_padded, uint32_t* bits, unsigned long long* count,
+                                 hipStream_t stream);
+/* out = a & b (XGM_FILTER_AND), a | b (_OR) or a & ~b (_AND_NOT) over two such bitmaps of n_words_padded words; *count (zeroed by the caller) += set bits */
+int xgm_launch_filter_combine(const uint32_t* a, const uint32_t* b, uint32_t op, uint32_t n_words_padded, uint32_t* out, unsigned long long* count,
+                              hipStream_t stream);
 /* a filter's bitmap as the whole query (xgm_range.h, xgm_search_range): the first k passing documents by docid (ord NULL) or by (value, docid)
  * under ord / reverse, counts of the passing documents per ordinal of spy_ord (NULL: none).  work = xgm_range_work_layout(...).total device
  * bytes, 256-byte aligned; afterwards [o_counts, o_pairs) holds the spy counters, the header, k hits and k ordinals — one copy back. */

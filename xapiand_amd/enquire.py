@@ -260,7 +260,14 @@ class Database:
         arr = (_lib.ValueRange * max(1, n))(*[_lib.ValueRange(r[0], r[1], r[2], r[3] if len(r) > 3 else _lib.XGM_RANGE_VALUE) for r in ranges])
         h, nd = C.c_void_p(), C.c_uint64()
         _lib.check(_lib.lib().xgm_filter_build(self._h, arr, n, C.byref(h), C.byref(nd)))
-        return Filter(h, nd.value, (self._info.lastdocid + 32) // 32)
+        return Filter(h, nd.value, (self._info.lastdocid + 32) // 32, self)
+
+    def build_query_filter(self, planned):
+        """xgm_filter_build_query: the match set of a planned, non-positional query (the docids search_all lists for it) as a bitmap on the
+        device → Filter; every consumer of a range filter takes it, and Filter.combine joins it with others."""
+        h, nd = C.c_void_p(), C.c_uint64()
+        _lib.check(_lib.lib().xgm_filter_build_query(self._h, C.byref(planned), C.byref(h), C.byref(nd)))
+        return Filter(h, nd.value, (self._info.lastdocid + 32) // 32, self)
 
     def set_stream(self, hip_stream):
         _lib.check(_lib.lib().xgm_index_set_stream(self._h, C.c_void_p(hip_stream)))
@@ -281,10 +288,19 @@ class Database:
 
 
 class Filter:
-    """A value-range filter on the device (Database.build_filter): immutable; n_docs = the documents it lets through."""
+    """A filter on the device — value ranges (Database.build_filter), a query's match set (Database.build_query_filter) or two filters
+    combined: immutable; n_docs = the documents it lets through."""
 
-    def __init__(self, handle, n_docs, n_words):
-        self._h, self.n_docs, self._n_words = handle, n_docs, n_words
+    def __init__(self, handle, n_docs, n_words, db=None):
+        self._h, self.n_docs, self._n_words, self._db = handle, n_docs, n_words, db
+
+    def combine(self, other, op, db=None):
+        """xgm_filter_combine: self & other (_lib.XGM_FILTER_AND), self | other (_OR) or self & ~other (_AND_NOT) as a new Filter; both stay as
+        they are.  db: the Database the filters belong to (a filter remembers the one that built it)."""
+        db = db or self._db or other._db
+        h, nd = C.c_void_p(), C.c_uint64()
+        _lib.check(_lib.lib().xgm_filter_combine(db._h, op, self._h, other._h, C.byref(h), C.byref(nd)))
+        return Filter(h, nd.value, self._n_words, db)
 
     def words(self):
         """xgm_filter_read: the bitmap as a list of 32-bit words, bit d & 31 of word d >> 5 set when document d passes."""
@@ -533,6 +549,21 @@ def column_ord_range(path, begin, end):
 def _spy_args(spy):
     """spy = None | (spy_slot, n_distinct) → (slot argument, counters per query)"""
     return (-1, 0) if spy is None else (spy[0], spy[1] + 1)
+
+
+def filter_and(db, a, b):
+    """a & b (xgm_filter_combine)."""
+    return a.combine(b, _lib.XGM_FILTER_AND, db)
+
+
+def filter_or(db, a, b):
+    """a | b"""
+    return a.combine(b, _lib.XGM_FILTER_OR, db)
+
+
+def filter_and_not(db, a, b):
+    """a & ~b"""
+    return a.combine(b, _lib.XGM_FILTER_AND_NOT, db)
 
 
 def search_filtered(db, planned, flt, sort_by=None, slot=0, reverse=False, spy=None):
