@@ -900,6 +900,21 @@ int xgm_debug_host_ns(uint64_t* out8);
 
 /* Diagnostics: out2 = {xgm_search_replay calls walked by one workgroup, calls walked by segments in parallel} of this process. */
 int xgm_debug_replay_info(uint64_t* out2);
+/* Diagnostics / tests: a caller's own list through the launch code of xgm_search_replay — no index, no segment, no query.  list[0 .. n) in ascending
+ * docid order on the host (bit 31 of subqs_matched flags an entry that is NOT a match: a document of the underlying conjunction that fails the
+ * positional test, as XGM_REPLAY_FROZEN_WEIGHT's list carries them); k = first + maxitems, check_at_least and mode as xgm_search_replay is given them.
+ * seg_min: 0 = the one-workgroup kernel; otherwise the shortest segment of the parallel formulation (what XGM_REPLAY_SEG_MIN sets, at least 64).
+ * hits[0 .. out->n_hits) = the page in rank order.  One workgroup: every figure, the matching documents counted from the flags.  By segments:
+ * known_matching_docs, n_hits and parallel = 1 (the others 0: ProtoMSet's max_weight is the match's there).
+ * XGM_E_INVALID where xgm_search_replay would not have walked the list so: seg_min != 0 with XGM_REPLAY_FROZEN_WEIGHT, k == 0, check_at_least > k
+ * or n < 4 * max(seg_min, k + 64); k > XGM_MAX_K either way. */
+typedef struct {
+    uint64_t known_matching_docs;
+    double max_weight, frozen_weight;       /* ProtoMSet::max_weight; the weight served after the freeze (0 if none was read) */
+    uint32_t n_hits, max_weight_subqs, frozen, parallel;
+} xgm_replay_figures;                       /* 40 bytes */
+int xgm_debug_replay_list(int device, const xgm_hit* list, uint64_t n, uint32_t k, uint64_t check_at_least, uint32_t mode, uint64_t seg_min,
+                          xgm_hit* hits, xgm_replay_figures* out);
 /* Diagnostics: out3 = {rows with XGM_REPLAY_BATCH_* bits the listing kernel took, rows it declined on the device, rows answered by xgm_search_replay when their
  * batch was collected} of this process. */
 int xgm_debug_batch_replay_info(uint64_t* out3);

@@ -18,6 +18,7 @@ XGM_OP_AND_NOT, XGM_OP_AND_MAYBE, XGM_OP_FILTER, XGM_OP_NEAR = 4, 5, 6, 7
 XGM_REPLAY_BATCH_COUNT = 2
 XGM_REPLAY_BATCH_FROZEN = 1         # xgm_query.replay / xgm_query_desc.replay (include/xgm.h)
 XGM_KNOWN_LOWER_BOUND = 1 << 63
+XGM_ALL_NOT_A_MATCH = 0x80000000    # subqs_matched of a list entry that is not a match (xgm_debug_replay_list)
 XGM_MATCHES_LOWER_BOUND = 1 << 63    # xgm_result_hdr.matches_exact: the count is a lower bound (include/xgm.h)
 XGM_DEVICE_NONE = -1          # xgm_index_open: dictionary and statistics only (host memory), no searches
 UINT64_MAX = (1 << 64) - 1
@@ -118,7 +119,12 @@ class PairCount(C.Structure):
     _fields_ = [("ord_a", C.c_uint32), ("ord_b", C.c_uint32), ("count", C.c_uint32), ("reserved", C.c_uint32)]
 
 
-assert C.sizeof(Hit) == 16 and C.sizeof(ResultHdr) == 32 and C.sizeof(PairCount) == 16
+class ReplayFigures(C.Structure):
+    _fields_ = [("known_matching_docs", C.c_uint64), ("max_weight", C.c_double), ("frozen_weight", C.c_double),
+                ("n_hits", C.c_uint32), ("max_weight_subqs", C.c_uint32), ("frozen", C.c_uint32), ("parallel", C.c_uint32)]
+
+
+assert C.sizeof(Hit) == 16 and C.sizeof(ResultHdr) == 32 and C.sizeof(PairCount) == 16 and C.sizeof(ReplayFigures) == 40
 
 # every symbol include/xgm.h declares: (name, restype, argtypes)
 _P = C.POINTER
@@ -171,6 +177,7 @@ _API = [
     ("xgm_search_all", C.c_int, [C.c_void_p, _P(Query), _P(Hit), C.c_uint64, _P(C.c_uint64), _P(ResultHdr)]),
     ("xgm_search_replay", C.c_int, [C.c_void_p, _P(Query), C.c_uint32, _P(Hit), _P(ResultHdr), _P(C.c_uint64)]),
     ("xgm_debug_replay_info", C.c_int, [_P(C.c_uint64)]),
+    ("xgm_debug_replay_list", C.c_int, [C.c_int, _P(Hit), C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64, _P(Hit), _P(ReplayFigures)]),
     ("xgm_debug_batch_replay_info", C.c_int, [_P(C.c_uint64)]),
     ("xgm_search_batch", C.c_int, [C.c_void_p, _P(Query), C.c_uint32, C.c_uint32, _P(Hit), _P(ResultHdr)]),
     ("xgm_search_batch_known", C.c_int, [C.c_void_p, _P(Query), C.c_uint32, C.c_uint32, _P(Hit), _P(ResultHdr), _P(C.c_uint64)]),

@@ -2727,6 +2727,44 @@ constexpr uint32_t kReplaySegments = 512u;           /* at most: one wave each; 
 static std::atomic<uint64_t> g_replays[2];          /* diagnostics: replays walked by one workgroup / by segments in parallel */
 extern "C" int xgm_debug_replay_info(uint64_t* out2) { if (!out2) return -1; out2[0] = g_replays[0].load(); out2[1] = g_replays[1].load(); return 0; }
 
+/* Device room behind the list: [the page | xgm_replay_out 128 B | the parallel formulation's count 128 B] = what is downloaded, then — where the
+ * parallel formulation may run — its scratch for up to kReplaySegments segment states. */
+static size_t replay_page_bytes(uint32_t k) { return ((size_t)std::max(k, 1u) * sizeof(xgm_hit) + 255) & ~(size_t)255; }
+static size_t replay_ext_bytes(uint32_t k, bool may_parallel) {
+    return replay_page_bytes(k) + 256 + (may_parallel ? xgm_replay_parallel_bytes(kReplaySegments, k) : 0);
+}
+
+struct ReplayFigures { xgm_replay_out o; uint64_t known; bool parallel; };
+
+/* One list in docid order (device, n >= 1 entries of which m match), replayed and its answer downloaded: the choice between the two formulations, the
+ * launch, the page into hits[0 .. r->o.n_hits) and the figures into *r.  seg_min: 0 = one workgroup; otherwise the parallel formulation's shortest
+ * segment — taken by the counting mode with 1 <= k, check_at_least <= k and a list of at least four segments, each longer than the page.
+ * d_ext: replay_ext_bytes(k, seg_min != 0) device bytes; *h_down: pinned, grown here. */
+static int replay_device_list(const xgm_hit* d_list, uint64_t n, uint64_t m, uint32_t k, uint64_t check_at_least, uint32_t mode, uint64_t seg_min,
+                              unsigned char* d_ext, hipStream_t stream, void** h_down, size_t* cap_down, xgm_hit* hits, ReplayFigures* r) {
+    int rc;
+    const size_t b_hits = replay_page_bytes(k), b_down = b_hits + 256;
+    xgm_hit* d_page = (xgm_hit*)d_ext;
+    xgm_replay_out* d_out = (xgm_replay_out*)(d_ext + b_hits);
+    unsigned long long* d_known = (unsigned long long*)(d_ext + b_hits + 128);
+    const uint64_t seg = std::max<uint64_t>(seg_min, (uint64_t)k + 64u);
+    const bool parallel = seg_min != 0u && mode == XGM_REPLAY_COUNT && k >= 1u && check_at_least <= k && n >= 4u * seg;
+    r->parallel = parallel;
+    if (parallel) {
+        const uint32_t S = (uint32_t)std::min<uint64_t>(kReplaySegments, n / seg);
+        const uint64_t seg_len = (((n + S - 1u) / S) + 63u) & ~(uint64_t)63;
+        if ((rc = xgm_launch_replay_parallel(d_list, n, k, check_at_least, S, seg_len, d_ext + b_down, d_page, d_out, d_known, stream))) return rc;
+    } else if ((rc = xgm_launch_replay(d_list, n, k, check_at_least, mode == XGM_REPLAY_FROZEN_WEIGHT, m, d_page, d_out, stream))) return rc;
+    if ((rc = grow_pinned(h_down, cap_down, b_down))) return rc;
+    HIP_TRY(hipMemcpyAsync(*h_down, d_ext, b_down, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    r->o = *(const xgm_replay_out*)((unsigned char*)*h_down + b_hits);
+    if (r->o.n_hits > k) return xgm_set_error(XGM_E_DEVICE, "xgm_search_replay: %u documents kept for a page of %u", r->o.n_hits, k);
+    memcpy(hits, *h_down, (size_t)r->o.n_hits * sizeof(xgm_hit));
+    r->known = parallel ? *(const unsigned long long*)((unsigned char*)*h_down + b_hits + 128) : r->o.known_matching_docs;
+    return XGM_OK;
+}
+
 extern "C" int xgm_search_replay(xgm_index* idx, const xgm_query* q, uint32_t mode, xgm_hit* hits, xgm_result_hdr* hdr, uint64_t* known_matching_docs) {
     if (!idx || !q || !hdr || !known_matching_docs || mode > XGM_REPLAY_FROZEN_WEIGHT) return xgm_set_error(XGM_E_INVALID, "bad argument");
     if (idx->device == XGM_DEVICE_NONE) return xgm_set_error(XGM_E_NO_DEVICE, "index opened without a device");
@@ -2753,41 +2791,62 @@ extern "C" int xgm_search_replay(xgm_index* idx, const xgm_query* q, uint32_t mo
      * function of the prefix: check_at_least within the page; scratch for up to 256 segment states rides behind the page (XGM_REPLAY_SERIAL=1: A/B) */
     static const bool serial_only = getenv("XGM_REPLAY_SERIAL") != nullptr;
     const bool may_parallel = mode == XGM_REPLAY_COUNT && k >= 1u && q->check_at_least <= k && !serial_only;
-    const size_t b_hits = ((size_t)std::max(k, 1u) * sizeof(xgm_hit) + 255) & ~(size_t)255, b_down = b_hits + 256;
-    const size_t ext = b_down + (may_parallel ? xgm_replay_parallel_bytes(kReplaySegments, k) : 0);
+    const size_t ext = replay_ext_bytes(k, may_parallel);
     if ((rc = search_all_device(idx, q, sc, mode == XGM_REPLAY_FROZEN_WEIGHT, cap_dev, &d_list, &n, &m, hdr, ext, &d_ext))) return rc;
     if (n > cap_dev) return xgm_set_error(XGM_E_DEVICE, "xgm_search_replay: %llu documents exceed the plan's upper bound %u", (unsigned long long)n, q->est_max);
     hdr->n_hits = 0;
     if (n == 0) return XGM_OK;
-    xgm_hit* d_page = (xgm_hit*)d_ext;
-    xgm_replay_out* d_out = (xgm_replay_out*)(d_ext + b_hits);
-    unsigned long long* d_known = (unsigned long long*)(d_ext + b_hits + 128);
     /* segments of >= 4 096 entries (XGM_REPLAY_SEG_MIN: the tests run small lists through the parallel path), longer than the page, at least four */
     static const uint64_t seg_min_env = getenv("XGM_REPLAY_SEG_MIN") ? (uint64_t)std::max(64, atoi(getenv("XGM_REPLAY_SEG_MIN"))) : 4096u;
-    const uint64_t seg_min = std::max<uint64_t>(seg_min_env, (uint64_t)k + 64u);
-    const bool parallel = may_parallel && n >= 4u * seg_min;
-    ++g_replays[parallel ? 1 : 0];
-    if (parallel) {
-        const uint32_t S = (uint32_t)std::min<uint64_t>(kReplaySegments, n / seg_min);
-        const uint64_t seg_len = (((n + S - 1u) / S) + 63u) & ~(uint64_t)63;
-        if ((rc = xgm_launch_replay_parallel(d_list, n, k, q->check_at_least, S, seg_len, d_ext + b_down, d_page, d_out, d_known, sc->stream))) return rc;
-    } else if ((rc = xgm_launch_replay(d_list, n, k, q->check_at_least, mode == XGM_REPLAY_FROZEN_WEIGHT, m, d_page, d_out, sc->stream))) return rc;
-    if ((rc = grow_pinned(&sc->h_down, &sc->cap_down, b_down))) return rc;
-    HIP_TRY(hipMemcpyAsync(sc->h_down, d_ext, b_down, hipMemcpyDeviceToHost, sc->stream));
-    HIP_TRY(hipStreamSynchronize(sc->stream));
-    const xgm_replay_out* o = (const xgm_replay_out*)((unsigned char*)sc->h_down + b_hits);
-    if (o->n_hits > k) return xgm_set_error(XGM_E_DEVICE, "xgm_search_replay: %u documents kept for a page of %u", o->n_hits, k);
-    memcpy(hits, sc->h_down, (size_t)o->n_hits * sizeof(xgm_hit));
-    hdr->n_hits = o->n_hits;
-    if (parallel) {
-        /* (the counting mode shows ProtoMSet the true weights: its max_weight is the match's, already in hdr from the unit headers) */
-        *known_matching_docs = *(const unsigned long long*)((unsigned char*)sc->h_down + b_hits + 128);
-        return XGM_OK;
-    }
-    *known_matching_docs = o->known_matching_docs;
+    ReplayFigures r;
+    if ((rc = replay_device_list(d_list, n, m, k, q->check_at_least, mode, may_parallel ? seg_min_env : 0u, d_ext, sc->stream, &sc->h_down, &sc->cap_down, hits, &r))) return rc;
+    ++g_replays[r.parallel ? 1 : 0];
+    hdr->n_hits = r.o.n_hits;
+    *known_matching_docs = r.known;
+    if (r.parallel) return XGM_OK;        /* (the counting mode shows ProtoMSet the true weights: its max_weight is the match's, already in hdr from the unit headers) */
     /* ProtoMSet's own max_weight (update_max_weight sees what add() is shown: the frozen weight where it was served) */
-    hdr->max_attained = o->max_weight;
-    hdr->max_weight_subqs_matched = o->max_weight_subqs;
+    hdr->max_attained = r.o.max_weight;
+    hdr->max_weight_subqs_matched = r.o.max_weight_subqs;
+    return XGM_OK;
+}
+
+/* Diagnostics (include/xgm.h): a caller's own list through the same launch code, no index behind it. */
+extern "C" int xgm_debug_replay_list(int device, const xgm_hit* list, uint64_t n, uint32_t k, uint64_t check_at_least, uint32_t mode, uint64_t seg_min,
+                                     xgm_hit* hits, xgm_replay_figures* out) {
+    if (!out || (n && !list) || mode > XGM_REPLAY_FROZEN_WEIGHT || k > XGM_MAX_K || (k && !hits)) return xgm_set_error(XGM_E_INVALID, "bad argument");
+    memset(out, 0, sizeof *out);
+    const bool want_parallel = seg_min != 0u;
+    if (want_parallel) {
+        /* where xgm_search_replay would have walked the list in one workgroup there is no parallel answer to give */
+        seg_min = std::max<uint64_t>(seg_min, 64u);
+        if (mode != XGM_REPLAY_COUNT || k == 0u || check_at_least > k || n < 4u * std::max<uint64_t>(seg_min, (uint64_t)k + 64u))
+            return xgm_set_error(XGM_E_INVALID, "xgm_debug_replay_list: xgm_search_replay does not walk such a list by segments");
+    }
+    if (n == 0) return XGM_OK;
+    int rc = use_device(device);
+    if (rc) return rc;
+    uint64_t m = 0;
+    for (uint64_t i = 0; i < n; ++i) m += (list[i].subqs_matched & XGM_ALL_NOT_A_MATCH) ? 0u : 1u;
+    struct Held {                            /* freed on every way out */
+        hipStream_t stream = nullptr; void* h_down = nullptr;
+        ~Held() { if (stream) hipStreamDestroy(stream); if (h_down) hipHostFree(h_down); }
+    } held;
+    DeviceBuffers bufs;
+    xgm_hit* d_list = nullptr;
+    unsigned char* d_ext = nullptr;
+    if ((rc = bufs.alloc((void**)&d_list, (size_t)n * sizeof(xgm_hit)))) return rc;
+    if ((rc = bufs.alloc((void**)&d_ext, replay_ext_bytes(k, want_parallel)))) return rc;
+    HIP_TRY(hipStreamCreateWithFlags(&held.stream, hipStreamNonBlocking));
+    HIP_TRY(hipMemcpyAsync(d_list, list, (size_t)n * sizeof(xgm_hit), hipMemcpyHostToDevice, held.stream));
+    size_t cap_down = 0;
+    ReplayFigures r;
+    rc = replay_device_list(d_list, n, m, k, check_at_least, mode, seg_min, d_ext, held.stream, &held.h_down, &cap_down, hits, &r);
+    if (rc) { hipStreamSynchronize(held.stream); return rc; }
+    if (r.parallel != want_parallel) return xgm_set_error(XGM_E_DEVICE, "xgm_debug_replay_list: the other formulation ran");
+    out->known_matching_docs = r.known;
+    out->n_hits = r.o.n_hits;
+    out->parallel = r.parallel ? 1u : 0u;
+    if (!r.parallel) { out->max_weight = r.o.max_weight; out->max_weight_subqs = r.o.max_weight_subqs; out->frozen = r.o.frozen; out->frozen_weight = r.o.frozen_weight; }
     return XGM_OK;
 }
 

@@ -691,6 +691,26 @@ def search_replay(db, planned, mode=REPLAY_COUNT):
     return [(hits[i].docid, hits[i].weight, hits[i].subqs_matched) for i in range(hdr.n_hits)], hdr, known.value
 
 
+def replay_list(hits, k, check_at_least=0, mode=REPLAY_COUNT, seg_min=0, device=0):
+    """xgm_debug_replay_list: a caller's own list [(docid, weight, subqs)] (ascending docids; subqs may carry _lib.XGM_ALL_NOT_A_MATCH), a ready
+    (_lib.Hit * n) array or a numpy record array of 16-byte items laid out as xgm_hit, through xgm_search_replay's launch code: seg_min = 0 the one-workgroup kernel, otherwise the parallel formulation with segments
+    of at least seg_min entries.  Returns ([(docid, weight, subqs)] = the page in rank order, _lib.ReplayFigures)."""
+    if isinstance(hits, C.Array):
+        arr, n = hits, len(hits)
+    elif hasattr(hits, "ctypes"):                 # a numpy record array laid out as xgm_hit (16-byte items)
+        assert hits.itemsize == C.sizeof(_lib.Hit) and hits.flags["C_CONTIGUOUS"]
+        arr, n = hits.ctypes.data_as(C.POINTER(_lib.Hit)), len(hits)
+    else:
+        n = len(hits)
+        arr = (_lib.Hit * max(1, n))()
+        for i, (d, w, m) in enumerate(hits):
+            arr[i].docid, arr[i].weight, arr[i].subqs_matched = d, w, m
+    page = (_lib.Hit * max(1, k))()
+    fig = _lib.ReplayFigures()
+    _lib.check(_lib.lib().xgm_debug_replay_list(device, arr, n, k, check_at_least, mode, seg_min, page, C.byref(fig)))
+    return [(page[i].docid, page[i].weight, page[i].subqs_matched) for i in range(fig.n_hits)], fig
+
+
 def search_batch_replay(db, plans, replay=_lib.XGM_REPLAY_BATCH_FROZEN):
     """A batch in flight whose queries carry XGM_REPLAY_BATCH_* bits (xgm_search_batch_begin / xgm_batch_end / xgm_batch_known): the reference's own
     answers at batch throughput → list of ([(docid, weight, subqs)], hdr, known_matching_docs incl. XGM_KNOWN_LOWER_BOUND)."""
