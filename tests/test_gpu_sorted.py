@@ -60,7 +60,9 @@ def test_value_sorts_vs_oracle(built, tmp_path, stripe_bits):
 
 def test_sorted_batch_equals_single_searches_and_the_oracle(built, tmp_path):
     """xgm_search_sorted_batch (round 5): >= 64 searches of mixed shapes and page sizes under ONE sort in one launch give what
-    xgm_search_sorted gives for each (hits, ordinals, match count, best weight) — and a sample of them what the pinned oracle gives."""
+    xgm_search_sorted gives for each (hits, ordinals, match count, best weight) — and every one of them, under every sort, what the pinned oracle
+    gives: the single search is the batch's own code with nq = 1, so the first comparison checks the stride and offset arithmetic of that path,
+    the second the ranking."""
     c = H.Corpus(*((3000, 8000) if QUICK else (30000, 60000)))
     db = Database(c.build_segment(str(tmp_path / "b.seg")))
     values = {}
@@ -82,13 +84,12 @@ def test_sorted_batch_equals_single_searches_and_the_oracle(built, tmp_path):
             one, ohdr = search_sorted(db, p, MODES[mode], slot, rev)
             assert got == one, (q, mode)
             assert (hdr.n_hits, hdr.matches_exact, hdr.max_attained, hdr.max_weight_subqs_matched) == (ohdr.n_hits, ohdr.matches_exact, ohdr.max_attained, ohdr.max_weight_subqs_matched), q
-            if qi % 5 == 0:
-                want, whdr = H.oracle_search_sorted(c, q["op"], q["terms"], q["first"], q["maxitems"], mode, slot, rev, n_required=q.get("n_required", 0))
-                assert [(d, w, m) for d, w, m, _ in got] == [(d, w, m) for d, w, m, _ in want], (q, mode, slot, rev)
-                assert [values[slot][o - 1] if o else b"" for _, _, _, o in got] == [k for _, _, _, k in want], (q, mode, slot, rev)
-                assert hdr.matches_exact == whdr.matches
-                checked += 1
-    assert checked >= (9 if QUICK else 36)
+            want, whdr = H.oracle_search_sorted(c, q["op"], q["terms"], q["first"], q["maxitems"], mode, slot, rev, n_required=q.get("n_required", 0))
+            assert [(d, w, m) for d, w, m, _ in got] == [(d, w, m) for d, w, m, _ in want], (q, mode, slot, rev)
+            assert [values[slot][o - 1] if o else b"" for _, _, _, o in got] == [k for _, _, _, k in want], (q, mode, slot, rev)
+            assert hdr.matches_exact == whdr.matches
+            checked += 1
+    assert checked >= 3 * len(base)
     # ... and with a ValueCountMatchSpy riding on every search of the batch: the page of the plain batch, the counts of the single spied search
     from xapiand_amd.enquire import search_sorted_spy, search_sorted_spy_batch
     nd = len(values[1])
@@ -312,6 +313,36 @@ def test_enquire_mirror_against_the_references_own_msets(built, tmp_path):
         enq.add_matchspy(spy)
         enq.get_mset(q["first"], q["maxitems"])
         assert spy.get_total() == r["spy_total"] and [[v.hex(), n] for v, n in spy.values()] == r["spy"], q
+    db.close()
+    c.close()
+
+
+def test_single_sorted_search_of_a_plan_in_parts(built, tmp_path):
+    """A query whose units exceed one merge's capacity is planned in parts (plan_batch: pseudo-query p * nq + q of the unit offsets).  The
+    single sorted search walks the units of every part and answers; the batch entry point declines such a plan, for one query too.
+    No diagnostic shows the sorted plan, so that it has more than one part is derived here from the planner's constants: a unit's run table
+    (16 KiB, 8 B per term and stripe) holds at most 16384 / (8 * 16) = 128 stripes of a 16-term query — fewer where the LDS is tight —, one
+    query may have XGM_MERGE_CAP / 2 / k = 8192 / 2 / 1024 = 4 units per part, and 513 stripes of 256 documents need at least 5 units."""
+    stripe_bits, n_terms, k = 8, 16, 1024
+    spg_most, units_per_part = 16384 // (8 * n_terms), 8192 // 2 // k
+    n_docs = (units_per_part * spg_most) << stripe_bits                 # the smallest lastdocid with one stripe more than four full units
+    c = H.Corpus(n_docs, 2000, len_lo=3, len_hi=6, positions=False)
+    db = Database(c.build_segment(str(tmp_path / "p.seg"), stripe_bits=stripe_bits))
+    n_stripes = (db.get_lastdocid() >> stripe_bits) + 1
+    assert -(-n_stripes // spg_most) > units_per_part, (db.get_lastdocid(), n_stripes)       # more than one part
+    p0 = write_column(c, 0, str(tmp_path / "col0"))
+    db.attach_column(p0)
+    values = read_column_values(p0)
+    terms = ["t%d" % r for r in range(1, n_terms + 1)]
+    p = plan(db, Query("OR", terms), 0, k)
+    want, whdr = H.oracle_search_sorted(c, "OR", terms, 0, k, "VR", 0, False)
+    got, hdr = search_sorted(db, p, MODES["VR"], 0, False)
+    assert len(got) == k
+    assert [(d, w, m) for d, w, m, _ in got] == [(d, w, m) for d, w, m, _ in want]
+    assert [values[o - 1] if o else b"" for _, _, _, o in got] == [key for _, _, _, key in want]
+    assert hdr.matches_exact == whdr.matches and hdr.max_attained == whdr.max_attained
+    with pytest.raises(_lib.XgmUnsupported):
+        search_sorted_batch(db, [p], MODES["VR"], 0, False)
     db.close()
     c.close()
 

@@ -1,7 +1,7 @@
 """Sorted and collapsed searches where their keys TIE and their buffers end.  Everything that is not plain relevance runs through one kernel,
 xgm_match_sorted_kernel (xgm_match_body.inc compiled a second time; sorted_before, topk_sort_sorted, collapse_prune in xgm_kernels.hip), and one host merge
-(sorted_core / sorted_batch_core in xgm_api.cc).  Its order — two 64-bit keys, then the docid ascending — is written down in the kernel's sort, in its `take`
-test against the k-th entry and in the host's two merges; its buffer has three sizes (512 / 1024 / 2048 entries for pages up to 256 / 768 / 1024); a collapse
+(sorted_batch_core in xgm_api.cc; the single entry points call it with nq = 1).  Its order — two 64-bit keys, then the docid ascending — is written down in
+the kernel's sort, in its `take` test against the k-th entry and in the host's merge; its buffer has three sizes (512 / 1024 / 2048 entries for pages up to 256 / 768 / 1024); a collapse
 key is collapsed in every unit and once more on the host.  On the synthetic corpus equal keys are accidents and no page is larger than about 300.
 
 Here they are the rule: the documents of tests/test_gpu_ties.py (8 stripes x 1024 documents of one length, wdf 1 or 2: classes of bit-identical weights across

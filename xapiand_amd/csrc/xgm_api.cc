@@ -187,6 +187,26 @@ static void scratch_destroy(XgmScratch* s) {
     delete s;
 }
 
+/* xgm_index_set_profiling: the next pair of events to record around a kernel (both NULL while profiling is off).  The index keeps the pairs it
+ * made, xgm_last_kernel_ms reads and rewinds them; a pair is created when every one is taken. */
+static int next_event_pair(xgm_index* idx, hipEvent_t* start, hipEvent_t* stop) {
+    *start = *stop = nullptr;
+    if (!idx->profiling) return XGM_OK;
+    std::lock_guard<std::mutex> lk(idx->scratch_mu);
+    if (idx->prof_used == idx->prof_events.size()) {
+        hipEvent_t a = nullptr, b = nullptr;
+        if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) {
+            if (a) hipEventDestroy(a);
+            return xgm_launch_error("profiling events", 0, "hipEventCreate");
+        }
+        idx->prof_events.push_back({a, b});
+    }
+    *start = (hipEvent_t)idx->prof_events[idx->prof_used].first;
+    *stop = (hipEvent_t)idx->prof_events[idx->prof_used].second;
+    ++idx->prof_used;
+    return XGM_OK;
+}
+
 /* ------------------------------------------------------------------ index lifetime ----------- */
 
 void xgm_shard_ctx_destroy(XgmShardCtx* c);
@@ -1148,18 +1168,7 @@ static int run_class_batch(xgm_index* idx, XgmScratch* s, hipStream_t stream, co
     L.tally = idx->tally;
     L.cand = s->d_cand; L.ghdr = s->d_ghdr;
     hipEvent_t pe0 = nullptr, pe1 = nullptr;
-    if (idx->profiling) {
-        std::lock_guard<std::mutex> lk(idx->scratch_mu);
-        if (idx->prof_used == idx->prof_events.size()) {
-            hipEvent_t a, b;
-            HIP_TRY(hipEventCreate(&a));
-            HIP_TRY(hipEventCreate(&b));
-            idx->prof_events.push_back({a, b});
-        }
-        pe0 = (hipEvent_t)idx->prof_events[idx->prof_used].first;
-        pe1 = (hipEvent_t)idx->prof_events[idx->prof_used].second;
-        ++idx->prof_used;
-    }
+    if ((rc = next_event_pair(idx, &pe0, &pe1))) return rc;
     idx->last_kernel = all ? "xgm_andw_all_kernel" : list ? "xgm_andw_list_kernel" : dense ? "xgm_dense_kernel" : bp.andw ? "xgm_andw_kernel" : bp.orw2 ? "xgm_orw2_kernel" : bp.orw ? "xgm_orw_kernel" : bp.and_only ? "xgm_and_kernel" : "xgm_match_kernel";
     idx->last_ghdr = s->d_ghdr; idx->last_n_work = bp.n_work;        /* xgm_last_batch_traffic */
     if (bp.orw || (bp.andw && bp.phrase)) {
@@ -1776,337 +1785,288 @@ struct DeviceBuffers {                       /* freed on every way out */
 };
 }  // namespace
 
-/* spy_slot >= 0: also count the matching documents by their value in that slot (counts[0 .. n_counts), n_counts = the column's
- * distinct values + 1).  collapse_slot >= 0: Enquire::set_collapse_key(collapse_slot, cmax) — the kernel collapses inside every
- * unit, the merge below once more; the per-key match counts (the spy mechanism on the collapse column) give the items' collapse
- * counts and the collapsed lower bound.  sort == NULL: by relevance. */
-static int sorted_core(xgm_index* idx, const xgm_query* q, const xgm_sort_spec* sort, xgm_hit* hits, uint32_t* hit_ord, xgm_result_hdr* hdr,
-                       int spy_slot, uint32_t* counts, uint32_t n_counts,
-                       int collapse_slot = -1, uint32_t cmax = 0, uint32_t* hit_cord = nullptr, uint32_t* hit_ccount = nullptr, uint64_t* collapsed_lb = nullptr,
-                       const xgm_filter* flt = nullptr) {
-    if (!idx || !q || !hits || !hdr) return xgm_set_error(XGM_E_INVALID, "null argument");
-    if (idx->device == XGM_DEVICE_NONE) return xgm_set_error(XGM_E_NO_DEVICE, "index opened without a device");
-    if (sort && (sort->sort_by < XGM_SORT_VALUE || sort->sort_by > XGM_SORT_RELEVANCE_VALUE)) return xgm_set_error(XGM_E_INVALID, "sort_by %u", sort->sort_by);
-    if (!sort && collapse_slot < 0 && spy_slot < 0 && !flt) return xgm_set_error(XGM_E_INVALID, "neither a sort nor a collapse key nor a spy");
-    if (collapse_slot >= 0 && (cmax == 0 || spy_slot >= 0)) return xgm_set_error(XGM_E_INVALID, "collapse_max 0, or a spy together with a collapse key");
-    if (flt) if (int frc = filter_usable(idx, flt)) return frc;
-    const uint32_t mode = sort ? sort->sort_by : 4u;
-    const bool reverse = sort && sort->reverse;
-    const uint32_t* d_ord = nullptr;
-    const uint32_t* d_spy_ord = nullptr;
-    const uint32_t* d_cord = nullptr;
-    std::vector<uint32_t> key_counts;
-    {
-        std::lock_guard<std::mutex> lk(idx->columns_mu);
-        if (sort) {
-            auto it = idx->columns.find(sort->slot);
-            if (it == idx->columns.end()) return XGM_UNSUPPORTED;
-            d_ord = (const uint32_t*)it->second.first;
-        }
-        if (spy_slot >= 0) {
-            auto it = idx->columns.find((uint32_t)spy_slot);
-            if (it == idx->columns.end()) return XGM_UNSUPPORTED;
-            if (!counts || n_counts != it->second.second + 1u) return xgm_set_error(XGM_E_INVALID, "spy: %u counters for a column of %u distinct values (+ 1 for no value)", n_counts, it->second.second);
-            d_spy_ord = (const uint32_t*)it->second.first;
-        }
-        if (collapse_slot >= 0) {
-            auto it = idx->columns.find((uint32_t)collapse_slot);
-            if (it == idx->columns.end()) return XGM_UNSUPPORTED;
-            d_cord = (const uint32_t*)it->second.first;
-            d_spy_ord = d_cord;                       /* matches per collapse key */
-            key_counts.assign((size_t)it->second.second + 1u, 0u);
-            counts = key_counts.data(); n_counts = (uint32_t)key_counts.size();
-        }
-    }
-    int rc = use_device(idx->device);
-    if (rc) return rc;
-    xgm_dev_query dq;
-    uint32_t kq = 0;
-    double mp = 0;
-    BatchPlan bp;
-    if ((rc = plan_batch(idx, q, 1, &dq, &kq, &mp, &bp, true))) return rc;
-    if (bp.andw || bp.orw || bp.and_only || dq.k == 0 || bp.cap > 8u * XGM_WG) return XGM_UNSUPPORTED;
-    if (xgm_match_sorted_smem_bytes(idx->hdr.stripe_bits - bp.sub_bits, bp.tab_terms, bp.phrase, bp.cap, bp.wide, bp.stripes_per_group) > 160u * 1024u) return XGM_UNSUPPORTED;
-    const uint32_t k = dq.k, n_work = bp.n_work;
-    /* per-call device and pinned buffers + a stream from the index's scratch pool (re-used across calls: no allocation, no null stream —
-     * searches of concurrent threads do not serialise): [query | work list] go up in one copy, [headers | counters | candidates] come down in one */
-    XgmScratch* sc;
-    if ((rc = scratch_acquire(idx, &sc))) return rc;
-    ScratchRelease release_{idx, sc};            /* (synchronises the stream before the scratch goes back to the pool: an error return leaves nothing in flight on it) */
-    hipStream_t stream = sc->stream;
-    const size_t o_q = 0, b_q = (sizeof dq + 15) & ~(size_t)15;
-    const size_t o_wk = o_q + b_q, b_wk = ((size_t)n_work * sizeof(xgm_work) + 15) & ~(size_t)15;
-    const size_t up_bytes = o_wk + b_wk;
-    const size_t o_gh = up_bytes, b_gh = (size_t)n_work * sizeof(xgm_group_hdr);
-    const size_t o_ct = o_gh + b_gh, b_ct = d_spy_ord ? (((size_t)n_counts * 4 + 15) & ~(size_t)15) : 0;
-    const size_t o_cd = o_ct + b_ct, b_cd = (size_t)n_work * k * sizeof(xgm_cand_sorted);
-    const size_t total = o_cd + b_cd;
-    if ((rc = grow(&sc->d_sorted, &sc->cap_sorted, total))) return rc;
-    if ((rc = grow_pinned(&sc->h_sorted, &sc->cap_hsorted, total))) return rc;
-    unsigned char* hb = (unsigned char*)sc->h_sorted;
-    memcpy(hb + o_q, &dq, sizeof dq);
-    memcpy(hb + o_wk, bp.work.data(), (size_t)n_work * sizeof(xgm_work));
-    HIP_TRY(hipMemcpyAsync(sc->d_sorted, hb, up_bytes, hipMemcpyHostToDevice, stream));
-    xgm_dev_query* d_q = (xgm_dev_query*)(sc->d_sorted + o_q);
-    xgm_work* d_work = (xgm_work*)(sc->d_sorted + o_wk);
-    xgm_group_hdr* d_ghdr = (xgm_group_hdr*)(sc->d_sorted + o_gh);
-    uint32_t* d_counts = d_spy_ord ? (uint32_t*)(sc->d_sorted + o_ct) : nullptr;
-    xgm_cand_sorted* d_cand = (xgm_cand_sorted*)(sc->d_sorted + o_cd);
-    if (d_counts) HIP_TRY(hipMemsetAsync(d_counts, 0, (size_t)n_counts * 4, stream));
-    xgm_match_launch L;
-    L.seg = idx->view;
-    L.queries = d_q;
-    L.nq = 1; L.n_work = n_work; L.work = d_work; L.stripes_per_group = bp.stripes_per_group; L.sub_bits = bp.sub_bits;
-    L.tab_terms = bp.tab_terms; L.cap = bp.cap; L.k_stride = k;
-    L.phrase = bp.phrase; L.wide = bp.wide; L.sided = 0;
-    L.cand = nullptr; L.ghdr = d_ghdr;
-    if ((rc = xgm_launch_match_sorted(L, d_ord, mode, reverse ? 1u : 0u, d_spy_ord, d_counts, d_cord, cmax, d_cand, stream, nullptr, nullptr, nullptr, 0,
-                                      flt ? flt->d_bits : nullptr)))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(hb + o_gh, sc->d_sorted + o_gh, total - o_gh, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    const xgm_group_hdr* gh = (const xgm_group_hdr*)(hb + o_gh);
-    const xgm_cand_sorted* cand = (const xgm_cand_sorted*)(hb + o_cd);
-    if (d_counts) memcpy(counts, hb + o_ct, (size_t)n_counts * 4);
-    /* merge the units: their best k each under the comparison the kernel used; the whole match's best weight and count */
-    std::vector<xgm_cand_sorted> all;
-    uint64_t matches = 0, max_w = 0;
-    uint32_t max_d = UINT32_MAX, max_m = 0;
-    for (uint32_t u = 0; u < n_work; ++u) {
-        const xgm_group_hdr& g = gh[u];
-        if (g.n_cand > k) return xgm_set_error(XGM_E_DEVICE, "sorted search: unit %u reports %u candidates for k = %u", u, g.n_cand, k);
-        matches += g.matches;
-        all.insert(all.end(), cand + (size_t)u * k, cand + (size_t)u * k + g.n_cand);
-        if (g.c_pad[0] != UINT32_MAX && (max_d == UINT32_MAX || g.c_pos > max_w || (g.c_pos == max_w && g.c_pad[0] < max_d))) { max_w = g.c_pos; max_d = g.c_pad[0]; max_m = g.c_pad[1]; }
-    }
-    const bool use_x = mode == XGM_SORT_VALUE_RELEVANCE || mode == XGM_SORT_RELEVANCE_VALUE;
-    std::sort(all.begin(), all.end(), [&](const xgm_cand_sorted& a, const xgm_cand_sorted& b) {
-        if (a.kw != b.kw) return a.kw > b.kw;
-        if (use_x && a.kx != b.kx) return a.kx > b.kx;
-        return a.did < b.did;
-    });
-    if (collapse_slot >= 0) {
-        /* the merged ranking collapsed once more: of every key the first cmax stay */
-        std::vector<uint32_t> kept_of(key_counts.size(), 0u);
-        size_t out = 0;
-        for (const xgm_cand_sorted& c : all) {
-            if (c.cord >= kept_of.size()) return xgm_set_error(XGM_E_DEVICE, "sorted search: collapse ordinal %u beyond the column", c.cord);
-            if (c.cord == 0u || kept_of[c.cord]++ < cmax) all[out++] = c;
-        }
-        all.resize(out);
-        if (collapsed_lb) {
-            /* Collapser::get_matches_lower_bound: documents without a key + per key the entries that stay */
-            uint64_t lb = key_counts[0];
-            for (size_t o = 1; o < key_counts.size(); ++o) lb += std::min<uint32_t>(key_counts[o], cmax);
-            *collapsed_lb = lb;
-        }
-    }
-    const uint32_t n = (uint32_t)std::min<size_t>(k, all.size());
-    const bool weight_first = mode >= XGM_SORT_RELEVANCE_VALUE;             /* relevance then value, relevance alone */
-    for (uint32_t i = 0; i < n; ++i) {
-        const uint64_t wbits = weight_first ? all[i].kw : all[i].kx;
-        const uint32_t okey = (uint32_t)(weight_first ? all[i].kx : all[i].kw);
-        hits[i].docid = all[i].did;
-        hits[i].subqs_matched = all[i].subqs;
-        memcpy(&hits[i].weight, &wbits, 8);
-        if (hit_ord) hit_ord[i] = sort ? (reverse ? okey : ~okey) : 0u;
-        if (hit_cord) hit_cord[i] = all[i].cord;
-        if (hit_ccount) hit_ccount[i] = (collapse_slot >= 0 && all[i].cord && key_counts[all[i].cord] > cmax) ? key_counts[all[i].cord] - cmax : 0u;
-    }
-    memset(hdr, 0, sizeof *hdr);
-    hdr->n_hits = n;
-    hdr->matches_exact = matches;
-    hdr->max_possible = q->max_possible;
-    if (max_d != UINT32_MAX) { memcpy(&hdr->max_attained, &max_w, 8); hdr->max_weight_subqs_matched = max_m; }
+/* A slot's plain column: its ordinals in HBM and the number of distinct values, or false when none is attached.  (A replaced column's array
+ * outlives the searches that copied its pointer: attach_ordinals.) */
+struct ColumnRef { const uint32_t* ord = nullptr; uint32_t n_distinct = 0; };
+static bool find_column(xgm_index* idx, uint32_t slot, ColumnRef* out) {
+    std::lock_guard<std::mutex> lk(idx->columns_mu);
+    auto it = idx->columns.find(slot);
+    if (it == idx->columns.end()) return false;
+    out->ord = (const uint32_t*)it->second.first;
+    out->n_distinct = it->second.second;
+    return true;
+}
+/* ... the column a ValueCountMatchSpy counts by: the caller's counters must be one per distinct value and one for "no value" */
+static int find_spy_column(xgm_index* idx, uint32_t slot, const uint32_t* counts, uint32_t n_counts, ColumnRef* out) {
+    if (!find_column(idx, slot, out)) return XGM_UNSUPPORTED;
+    if (!counts || n_counts != out->n_distinct + 1u)
+        return xgm_set_error(XGM_E_INVALID, "spy: %u counters for a column of %u distinct values (+ 1 for no value)", n_counts, out->n_distinct);
     return XGM_OK;
 }
 
-extern "C" int xgm_search_sorted(xgm_index* idx, const xgm_query* q, const xgm_sort_spec* sort, xgm_hit* hits, uint32_t* hit_ord,
-                                 xgm_result_hdr* hdr) {
-    if (!sort) return xgm_set_error(XGM_E_INVALID, "null argument");
-    return sorted_core(idx, q, sort, hits, hit_ord, hdr, -1, nullptr, 0);
+/* ---- the host side of xgm_match_sorted_kernel, shared by every sorted, spied, collapsed and filtered search and by search_all_device --------
+ * plan_sorted: the workgroup kernel's decomposition of the queries and what the sorted kernel declines.  k_limit: a caller's rows hold that many
+ * hits per query (a page beyond them is the caller's error); UINT32_MAX where there is no such bound. */
+static int plan_sorted(xgm_index* idx, const xgm_query* qs, uint32_t nq, uint32_t k_limit, xgm_dev_query* dq, BatchPlan* bp) {
+    std::vector<uint32_t> kq(nq);
+    std::vector<double> mp(nq);
+    int rc = plan_batch(idx, qs, nq, dq, kq.data(), mp.data(), bp, true);
+    if (rc) return rc;
+    if (bp->andw || bp->orw || bp->and_only || bp->cap > 8u * XGM_WG) return XGM_UNSUPPORTED;
+    for (uint32_t i = 0; i < nq; ++i) {
+        if (dq[i].k == 0) return XGM_UNSUPPORTED;
+        if (dq[i].k > k_limit) return xgm_set_error(XGM_E_INVALID, "k_stride %u < first + maxitems %u", k_limit, dq[i].k);
+    }
+    if (xgm_match_sorted_smem_bytes(idx->hdr.stripe_bits - bp->sub_bits, bp->tab_terms, bp->phrase, bp->cap, bp->wide, bp->stripes_per_group) > 160u * 1024u) return XGM_UNSUPPORTED;
+    return XGM_OK;
 }
 
-/* nq searches under ONE sort in ONE launch (include/xgm.h: xgm_search_sorted_batch): the workgroup kernel's units of every query go up in one
- * work list (plan_batch), every unit leaves its best k under the sort, the host merges each query's units — what xgm_search_sorted does
- * for one query, without a launch, an upload, a download and a synchronisation per query. */
-/* collapse_slot >= 0 (sorted_core's counterpart for a batch): the kernel collapses inside every unit, the merge below once more per query; the
- * matches per collapse key — the spy mechanism on the collapse column, one row per query — give the collapse counts and lower bounds */
-static int sorted_batch_core(xgm_index* idx, const xgm_query* qs, uint32_t nq, const xgm_sort_spec* sort, uint32_t k_stride, xgm_hit* hits,
-                             uint32_t* hit_ord, xgm_result_hdr* hdrs, int spy_slot, uint32_t* counts, uint32_t n_counts,
-                             int collapse_slot = -1, uint32_t cmax = 0, uint32_t* hit_cord = nullptr, uint32_t* hit_ccount = nullptr, uint64_t* collapsed_lb = nullptr,
-                             const xgm_filter* flt = nullptr) {
+/* The scratch's d_sorted and its pinned mirror h_sorted: [queries | work list] go up in one copy, [unit headers | candidates, kc per unit | counters]
+ * come down in one.  stage_sorted sizes both (pinned_extra bytes more on the host), enqueues the upload and fills the launch. */
+struct SortedStage {
+    size_t o_wk = 0, o_gh = 0, o_cd = 0, o_ct = 0, total = 0;
+    unsigned char* hb = nullptr;             /* h_sorted */
+    xgm_cand_sorted* d_cand = nullptr;
+    uint32_t* d_counts = nullptr;            /* NULL without counters */
+    xgm_match_launch L;
+};
+static int stage_sorted(xgm_index* idx, XgmScratch* sc, const xgm_dev_query* dq, uint32_t nq, const BatchPlan& bp, uint32_t kc, size_t count_bytes,
+                        size_t pinned_extra, SortedStage* st) {
+    int rc;
+    const uint32_t n_work = bp.n_work;
+    const size_t b_q = ((size_t)nq * sizeof(xgm_dev_query) + 15) & ~(size_t)15;
+    st->o_wk = b_q;
+    st->o_gh = st->o_wk + (((size_t)n_work * sizeof(xgm_work) + 15) & ~(size_t)15);
+    st->o_cd = st->o_gh + (size_t)n_work * sizeof(xgm_group_hdr);
+    st->o_ct = st->o_cd + (((size_t)n_work * kc * sizeof(xgm_cand_sorted) + 15) & ~(size_t)15);
+    st->total = st->o_ct + count_bytes;
+    if ((rc = grow(&sc->d_sorted, &sc->cap_sorted, st->total))) return rc;
+    if ((rc = grow_pinned(&sc->h_sorted, &sc->cap_hsorted, st->total + pinned_extra))) return rc;
+    st->hb = (unsigned char*)sc->h_sorted;
+    memcpy(st->hb, dq, (size_t)nq * sizeof(xgm_dev_query));
+    memcpy(st->hb + st->o_wk, bp.work.data(), (size_t)n_work * sizeof(xgm_work));
+    HIP_TRY(hipMemcpyAsync(sc->d_sorted, st->hb, st->o_gh, hipMemcpyHostToDevice, sc->stream));
+    st->d_cand = (xgm_cand_sorted*)(sc->d_sorted + st->o_cd);
+    st->d_counts = count_bytes ? (uint32_t*)(sc->d_sorted + st->o_ct) : nullptr;
+    xgm_match_launch& L = st->L;
+    L.seg = idx->view;
+    L.queries = (xgm_dev_query*)sc->d_sorted;
+    L.nq = nq; L.n_work = n_work; L.work = (xgm_work*)(sc->d_sorted + st->o_wk); L.stripes_per_group = bp.stripes_per_group; L.sub_bits = bp.sub_bits;
+    L.tab_terms = bp.tab_terms; L.cap = bp.cap; L.k_stride = kc;
+    L.phrase = bp.phrase; L.wide = bp.wide; L.sided = 0;
+    L.cand = nullptr; L.ghdr = (xgm_group_hdr*)(sc->d_sorted + st->o_gh);
+    idx->last_kernel = "xgm_match_sorted_kernel";
+    return XGM_OK;
+}
+
+/* What a query's unit headers say of its whole match: the count, and the best weight with its document — of equal weights the smaller docid */
+struct UnitFold {
+    uint64_t matches = 0, max_w = 0;
+    uint32_t max_d = UINT32_MAX, max_m = 0;
+    void add(const xgm_group_hdr* gh, uint32_t begin, uint32_t end) {
+        for (uint32_t u = begin; u < end; ++u) {
+            const xgm_group_hdr& g = gh[u];
+            matches += g.matches;
+            if (g.c_pad[0] != UINT32_MAX && (max_d == UINT32_MAX || g.c_pos > max_w || (g.c_pos == max_w && g.c_pad[0] < max_d))) { max_w = g.c_pos; max_d = g.c_pad[0]; max_m = g.c_pad[1]; }
+        }
+    }
+    void write(xgm_result_hdr* hdr, double max_possible) const {     /* (n_hits stays 0: the caller's) */
+        memset(hdr, 0, sizeof *hdr);
+        hdr->matches_exact = matches;
+        hdr->max_possible = max_possible;
+        if (max_d != UINT32_MAX) { memcpy(&hdr->max_attained, &max_w, 8); hdr->max_weight_subqs_matched = max_m; }
+    }
+};
+
+/* What a search adds to a ranking of nq queries; every entry point below fills in its own. */
+struct SortedOpts {
+    int spy_slot = -1;                       /* >= 0: a ValueCountMatchSpy on that slot: counts [nq][n_counts], n_counts = the column's distinct values + 1 */
+    uint32_t* counts = nullptr;
+    uint32_t n_counts = 0;
+    int collapse_slot = -1;                  /* >= 0: Enquire::set_collapse_key(collapse_slot, cmax) */
+    uint32_t cmax = 0;
+    uint32_t* hit_cord = nullptr;            /* per hit: its collapse ordinal, the documents collapsed under it; per query: the collapsed lower bound */
+    uint32_t* hit_ccount = nullptr;
+    uint64_t* collapsed_lb = nullptr;
+    const xgm_filter* flt = nullptr;         /* only documents whose bit is set match */
+    bool single = false;                     /* a single-search entry point: nq = 1, no k_stride (the arrays hold first + maxitems entries) */
+};
+
+/* nq searches under ONE sort (NULL: by relevance) in ONE launch: the workgroup kernel's units of every query go up in one work list
+ * (plan_batch), every unit leaves its best k under the sort, the host merges each query's units.  A spy: the kernel counts every matching
+ * document by its ordinal in the spy column, one row of counters per query.  A collapse key: the kernel collapses inside every unit, the
+ * merge below once more per query; the matches per collapse key — the spy mechanism on the collapse column — give the items' collapse
+ * counts and the collapsed lower bound. */
+static int sorted_batch_core(xgm_index* idx, const xgm_query* qs, uint32_t nq, const xgm_sort_spec* sort, uint32_t k_stride, xgm_hit* hits, uint32_t* hit_ord,
+                       xgm_result_hdr* hdrs, const SortedOpts& o) {
     if (!idx || !qs || !hits || !hdrs || nq == 0) return xgm_set_error(XGM_E_INVALID, "null argument");
-    if (!sort && collapse_slot < 0 && spy_slot < 0 && !flt) return xgm_set_error(XGM_E_INVALID, "neither a sort nor a collapse key nor a spy");
     if (idx->device == XGM_DEVICE_NONE) return xgm_set_error(XGM_E_NO_DEVICE, "index opened without a device");
-    if (flt) if (int frc = filter_usable(idx, flt)) return frc;
     if (sort && (sort->sort_by < XGM_SORT_VALUE || sort->sort_by > XGM_SORT_RELEVANCE_VALUE)) return xgm_set_error(XGM_E_INVALID, "sort_by %u", sort->sort_by);
-    if (collapse_slot >= 0 && (cmax == 0 || spy_slot >= 0)) return xgm_set_error(XGM_E_INVALID, "collapse_max 0, or a spy together with a collapse key");
+    if (!sort && o.collapse_slot < 0 && o.spy_slot < 0 && !o.flt) return xgm_set_error(XGM_E_INVALID, "neither a sort nor a collapse key nor a spy nor a filter");
+    if (o.collapse_slot >= 0 && (o.cmax == 0 || o.spy_slot >= 0)) return xgm_set_error(XGM_E_INVALID, "collapse_max 0, or a spy together with a collapse key");
+    if (o.flt) if (int frc = filter_usable(idx, o.flt)) return frc;
     const uint32_t mode = sort ? sort->sort_by : 4u;
     const bool reverse = sort && sort->reverse != 0;
-    const uint32_t* d_ord = nullptr;
-    const uint32_t* d_spy_ord = nullptr;
-    const uint32_t* d_cord = nullptr;
+    const uint32_t cmax = o.cmax;
+    ColumnRef by, tally, key;                                 /* the sort's column; the one matches are counted by; the collapse key's */
+    uint32_t* counts = nullptr;
+    uint32_t n_counts = 0;
     std::vector<uint32_t> key_counts;                         /* collapse: [nq][n_counts] matches per key */
-    {
-        std::lock_guard<std::mutex> lk(idx->columns_mu);
-        if (sort) {
-            auto it = idx->columns.find(sort->slot);
-            if (it == idx->columns.end()) return XGM_UNSUPPORTED;
-            d_ord = (const uint32_t*)it->second.first;
-        }
-        if (collapse_slot >= 0) {
-            auto it = idx->columns.find((uint32_t)collapse_slot);
-            if (it == idx->columns.end()) return XGM_UNSUPPORTED;
-            /* a row of counters per query: a column of many distinct keys under a large batch is left to single searches */
-            if (((size_t)it->second.second + 1u) * nq > ((size_t)64 << 20)) return XGM_UNSUPPORTED;
-            d_cord = (const uint32_t*)it->second.first;
-            d_spy_ord = d_cord;
-            n_counts = it->second.second + 1u;
-            key_counts.assign((size_t)n_counts * nq, 0u);
-            counts = key_counts.data();
-        }
-        if (spy_slot >= 0) {
-            auto sp = idx->columns.find((uint32_t)spy_slot);
-            if (sp == idx->columns.end()) return XGM_UNSUPPORTED;
-            if (!counts || n_counts != sp->second.second + 1u) return xgm_set_error(XGM_E_INVALID, "n_counts %u, the spy column has %u distinct values", n_counts, sp->second.second);
-            d_spy_ord = (const uint32_t*)sp->second.first;
-        }
+    if (sort && !find_column(idx, sort->slot, &by)) return XGM_UNSUPPORTED;
+    if (o.spy_slot >= 0) {
+        if (int src = find_spy_column(idx, (uint32_t)o.spy_slot, o.counts, o.n_counts, &tally)) return src;
+        counts = o.counts; n_counts = o.n_counts;
+    }
+    if (o.collapse_slot >= 0) {
+        if (!find_column(idx, (uint32_t)o.collapse_slot, &key)) return XGM_UNSUPPORTED;
+        /* a row of counters per query: a column of many distinct keys under a large batch is left to single searches */
+        if (!o.single && ((size_t)key.n_distinct + 1u) * nq > ((size_t)64 << 20)) return XGM_UNSUPPORTED;
+        tally = key;
+        n_counts = key.n_distinct + 1u;
+        key_counts.assign((size_t)n_counts * nq, 0u);
+        counts = key_counts.data();
     }
     int rc = use_device(idx->device);
     if (rc) return rc;
     std::vector<xgm_dev_query> dq(nq);
-    std::vector<uint32_t> kq(nq);
-    std::vector<double> mp(nq);
     BatchPlan bp;
-    if ((rc = plan_batch(idx, qs, nq, dq.data(), kq.data(), mp.data(), &bp, true))) return rc;
-    if (bp.andw || bp.orw || bp.and_only || bp.cap > 8u * XGM_WG || bp.parts != 1u) return XGM_UNSUPPORTED;
-    for (uint32_t i = 0; i < nq; ++i) if (dq[i].k == 0 || dq[i].k > k_stride) return dq[i].k ? xgm_set_error(XGM_E_INVALID, "k_stride %u < first + maxitems %u", k_stride, dq[i].k) : XGM_UNSUPPORTED;
-    if (xgm_match_sorted_smem_bytes(idx->hdr.stripe_bits - bp.sub_bits, bp.tab_terms, bp.phrase, bp.cap, bp.wide, bp.stripes_per_group) > 160u * 1024u) return XGM_UNSUPPORTED;
-    const uint32_t n_work = bp.n_work, kc = bp.k_stride_c;
+    if ((rc = plan_sorted(idx, qs, nq, o.single ? UINT32_MAX : k_stride, dq.data(), &bp))) return rc;
+    if (!o.single && bp.parts != 1u) return XGM_UNSUPPORTED;  /* (the batch entry points' own refusal; the merge below takes any number of parts) */
+    if (o.single) k_stride = dq[0].k;
+    const uint32_t kc = bp.k_stride_c;
+    /* per-call device and pinned buffers + a stream from the index's scratch pool (re-used across calls: no allocation, no null stream —
+     * searches of concurrent threads do not serialise) */
     XgmScratch* sc;
     if ((rc = scratch_acquire(idx, &sc))) return rc;
-    ScratchRelease release_{idx, sc};
+    ScratchRelease release_{idx, sc};            /* (synchronises the stream before the scratch goes back to the pool: an error return leaves nothing in flight on it) */
     hipStream_t stream = sc->stream;
-    const size_t o_q = 0, b_q = ((size_t)nq * sizeof(xgm_dev_query) + 15) & ~(size_t)15;
-    const size_t o_wk = o_q + b_q, b_wk = ((size_t)n_work * sizeof(xgm_work) + 15) & ~(size_t)15;
-    const size_t up_bytes = o_wk + b_wk;
-    const size_t o_gh = up_bytes, b_gh = (size_t)n_work * sizeof(xgm_group_hdr);
-    const size_t o_cd = o_gh + b_gh, b_cd = ((size_t)n_work * kc * sizeof(xgm_cand_sorted) + 15) & ~(size_t)15;
-    const size_t o_ct = o_cd + b_cd, b_ct = d_spy_ord ? (size_t)nq * n_counts * 4 : 0;          /* the spy: one row of counts per query */
-    const size_t total = o_ct + b_ct;
-    if ((rc = grow(&sc->d_sorted, &sc->cap_sorted, total))) return rc;
-    if ((rc = grow_pinned(&sc->h_sorted, &sc->cap_hsorted, total))) return rc;
-    unsigned char* hb = (unsigned char*)sc->h_sorted;
-    memcpy(hb + o_q, dq.data(), (size_t)nq * sizeof(xgm_dev_query));
-    memcpy(hb + o_wk, bp.work.data(), (size_t)n_work * sizeof(xgm_work));
-    HIP_TRY(hipMemcpyAsync(sc->d_sorted, hb, up_bytes, hipMemcpyHostToDevice, stream));
-    uint32_t* d_counts = d_spy_ord ? (uint32_t*)(sc->d_sorted + o_ct) : nullptr;
-    if (d_counts) HIP_TRY(hipMemsetAsync(d_counts, 0, b_ct, stream));
-    xgm_match_launch L;
-    L.seg = idx->view;
-    L.queries = (xgm_dev_query*)(sc->d_sorted + o_q);
-    L.nq = nq; L.n_work = n_work; L.work = (xgm_work*)(sc->d_sorted + o_wk); L.stripes_per_group = bp.stripes_per_group; L.sub_bits = bp.sub_bits;
-    L.tab_terms = bp.tab_terms; L.cap = bp.cap; L.k_stride = kc;
-    L.phrase = bp.phrase; L.wide = bp.wide; L.sided = 0;
-    L.cand = nullptr; L.ghdr = (xgm_group_hdr*)(sc->d_sorted + o_gh);
-    idx->last_kernel = "xgm_match_sorted_kernel";
-    L.spy_stride = d_counts ? n_counts : 0u;
-    if ((rc = xgm_launch_match_sorted(L, d_ord, mode, reverse ? 1u : 0u, d_spy_ord, d_counts, d_cord, d_cord ? cmax : 0u, (xgm_cand_sorted*)(sc->d_sorted + o_cd), stream,
-                                      nullptr, nullptr, nullptr, 0, flt ? flt->d_bits : nullptr)))
+    const size_t b_ct = tally.ord ? (size_t)nq * n_counts * 4 : 0;
+    SortedStage st;
+    if ((rc = stage_sorted(idx, sc, dq.data(), nq, bp, kc, b_ct, 0, &st))) return rc;
+    if (st.d_counts) HIP_TRY(hipMemsetAsync(st.d_counts, 0, b_ct, stream));
+    st.L.spy_stride = st.d_counts ? n_counts : 0u;
+    if ((rc = xgm_launch_match_sorted(st.L, by.ord, mode, reverse ? 1u : 0u, tally.ord, st.d_counts, key.ord, key.ord ? cmax : 0u, st.d_cand, stream, nullptr, nullptr,
+                                      nullptr, 0, o.flt ? o.flt->d_bits : nullptr)))
         return rc;
-    HIP_TRY(hipMemcpyAsync(hb + o_gh, sc->d_sorted + o_gh, total - o_gh, hipMemcpyDeviceToHost, stream));
+    unsigned char* hb = st.hb;
+    HIP_TRY(hipMemcpyAsync(hb + st.o_gh, sc->d_sorted + st.o_gh, st.total - st.o_gh, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
-    if (d_counts) memcpy(counts, hb + o_ct, b_ct);
-    const xgm_group_hdr* gh = (const xgm_group_hdr*)(hb + o_gh);
-    const xgm_cand_sorted* cand = (const xgm_cand_sorted*)(hb + o_cd);
+    if (st.d_counts) memcpy(counts, hb + st.o_ct, b_ct);
+    const xgm_group_hdr* gh = (const xgm_group_hdr*)(hb + st.o_gh);
+    const xgm_cand_sorted* cand = (const xgm_cand_sorted*)(hb + st.o_cd);
     const bool use_x = mode == XGM_SORT_VALUE_RELEVANCE || mode == XGM_SORT_RELEVANCE_VALUE;
-    const bool weight_first = mode >= XGM_SORT_RELEVANCE_VALUE;
+    const bool weight_first = mode >= XGM_SORT_RELEVANCE_VALUE;             /* relevance then value, relevance alone */
     std::vector<xgm_cand_sorted> all;
     for (uint32_t qi = 0; qi < nq; ++qi) {
+        /* merge the query's units — those of every part: slots goff[p * nq + qi] .. goff[p * nq + qi + 1] — their best k each under the
+         * comparison the kernel used; the whole match's best weight and count */
         const uint32_t k = dq[qi].k;
         all.clear();
-        uint64_t matches = 0, max_w = 0;
-        uint32_t max_d = UINT32_MAX, max_m = 0;
-        for (uint32_t u = bp.goff[qi]; u < bp.goff[qi + 1]; ++u) {
-            const xgm_group_hdr& g = gh[u];
-            if (g.n_cand > k) return xgm_set_error(XGM_E_DEVICE, "sorted batch: unit %u reports %u candidates for k = %u", u, g.n_cand, k);
-            matches += g.matches;
-            all.insert(all.end(), cand + (size_t)u * kc, cand + (size_t)u * kc + g.n_cand);
-            if (g.c_pad[0] != UINT32_MAX && (max_d == UINT32_MAX || g.c_pos > max_w || (g.c_pos == max_w && g.c_pad[0] < max_d))) { max_w = g.c_pos; max_d = g.c_pad[0]; max_m = g.c_pad[1]; }
+        UnitFold fold;
+        for (uint32_t p = 0; p < bp.parts; ++p) {
+            const uint32_t u0 = bp.goff[(size_t)p * nq + qi], u1 = bp.goff[(size_t)p * nq + qi + 1];
+            fold.add(gh, u0, u1);
+            for (uint32_t u = u0; u < u1; ++u) {
+                if (gh[u].n_cand > k) return xgm_set_error(XGM_E_DEVICE, "sorted search: unit %u reports %u candidates for k = %u", u, gh[u].n_cand, k);
+                all.insert(all.end(), cand + (size_t)u * kc, cand + (size_t)u * kc + gh[u].n_cand);
+            }
         }
         std::sort(all.begin(), all.end(), [&](const xgm_cand_sorted& a, const xgm_cand_sorted& b) {
             if (a.kw != b.kw) return a.kw > b.kw;
             if (use_x && a.kx != b.kx) return a.kx > b.kx;
             return a.did < b.did;
         });
-        const uint32_t* kc_q = d_cord ? counts + (size_t)qi * n_counts : nullptr;        /* this query's matches per collapse key */
-        if (d_cord) {
+        const uint32_t* kc_q = key.ord ? counts + (size_t)qi * n_counts : nullptr;        /* this query's matches per collapse key */
+        if (key.ord) {
             /* the merged ranking collapsed once more: of every key the first cmax stay */
             std::vector<uint32_t> kept_of(n_counts, 0u);
             size_t keep = 0;
             for (const xgm_cand_sorted& c : all) {
-                if (c.cord >= n_counts) return xgm_set_error(XGM_E_DEVICE, "sorted batch: collapse ordinal %u beyond the column", c.cord);
+                if (c.cord >= n_counts) return xgm_set_error(XGM_E_DEVICE, "sorted search: collapse ordinal %u beyond the column", c.cord);
                 if (c.cord == 0u || kept_of[c.cord]++ < cmax) all[keep++] = c;
             }
             all.resize(keep);
-            if (collapsed_lb) {
-                uint64_t lb = kc_q[0];                                       /* Collapser::get_matches_lower_bound */
-                for (uint32_t o = 1; o < n_counts; ++o) lb += std::min<uint32_t>(kc_q[o], cmax);
-                collapsed_lb[qi] = lb;
+            if (o.collapsed_lb) {
+                /* Collapser::get_matches_lower_bound: documents without a key + per key the entries that stay */
+                uint64_t lb = kc_q[0];
+                for (uint32_t c = 1; c < n_counts; ++c) lb += std::min<uint32_t>(kc_q[c], cmax);
+                o.collapsed_lb[qi] = lb;
             }
         }
         const uint32_t n = (uint32_t)std::min<size_t>(k, all.size());
-        xgm_hit* out = hits + (size_t)qi * k_stride;
+        const size_t row = (size_t)qi * k_stride;
         for (uint32_t i = 0; i < n; ++i) {
             const uint64_t wbits = weight_first ? all[i].kw : all[i].kx;
             const uint32_t okey = (uint32_t)(weight_first ? all[i].kx : all[i].kw);
-            out[i].docid = all[i].did;
-            out[i].subqs_matched = all[i].subqs;
-            memcpy(&out[i].weight, &wbits, 8);
-            if (hit_ord) hit_ord[(size_t)qi * k_stride + i] = sort ? (reverse ? okey : ~okey) : 0u;
-            if (hit_cord) hit_cord[(size_t)qi * k_stride + i] = all[i].cord;
-            if (hit_ccount) hit_ccount[(size_t)qi * k_stride + i] = (d_cord && all[i].cord && kc_q[all[i].cord] > cmax) ? kc_q[all[i].cord] - cmax : 0u;
+            hits[row + i].docid = all[i].did;
+            hits[row + i].subqs_matched = all[i].subqs;
+            memcpy(&hits[row + i].weight, &wbits, 8);
+            if (hit_ord) hit_ord[row + i] = sort ? (reverse ? okey : ~okey) : 0u;
+            if (o.hit_cord) o.hit_cord[row + i] = all[i].cord;
+            if (o.hit_ccount) o.hit_ccount[row + i] = (key.ord && all[i].cord && kc_q[all[i].cord] > cmax) ? kc_q[all[i].cord] - cmax : 0u;
         }
-        xgm_result_hdr* hdr = &hdrs[qi];
-        memset(hdr, 0, sizeof *hdr);
-        hdr->n_hits = n;
-        hdr->matches_exact = matches;
-        hdr->max_possible = qs[qi].max_possible;
-        if (max_d != UINT32_MAX) { memcpy(&hdr->max_attained, &max_w, 8); hdr->max_weight_subqs_matched = max_m; }
+        fold.write(&hdrs[qi], qs[qi].max_possible);
+        hdrs[qi].n_hits = n;
     }
     return XGM_OK;
 }
 
+extern "C" int xgm_search_sorted(xgm_index* idx, const xgm_query* q, const xgm_sort_spec* sort, xgm_hit* hits, uint32_t* hit_ord,
+                                 xgm_result_hdr* hdr) {
+    if (!sort) return xgm_set_error(XGM_E_INVALID, "null argument");
+    SortedOpts o;
+    o.single = true;
+    return sorted_batch_core(idx, q, 1, sort, 0, hits, hit_ord, hdr, o);
+}
+
+/* ... nq of them in one launch (include/xgm.h: xgm_search_sorted_batch): what xgm_search_sorted does for each, without a launch, an upload, a
+ * download and a synchronisation per query */
 extern "C" int xgm_search_sorted_batch(xgm_index* idx, const xgm_query* qs, uint32_t nq, const xgm_sort_spec* sort, uint32_t k_stride, xgm_hit* hits,
                                        uint32_t* hit_ord, xgm_result_hdr* hdrs) {
-    return sorted_batch_core(idx, qs, nq, sort, k_stride, hits, hit_ord, hdrs, -1, nullptr, 0);
+    return sorted_batch_core(idx, qs, nq, sort, k_stride, hits, hit_ord, hdrs, SortedOpts());
 }
 
-/* ... every search under Enquire::set_collapse_key(collapse_slot, collapse_max) (include/xgm.h: xgm_search_collapsed_batch) */
-extern "C" int xgm_search_collapsed_batch(xgm_index* idx, const xgm_query* qs, uint32_t nq, const xgm_sort_spec* sort, uint32_t collapse_slot,
-                                          uint32_t collapse_max, uint32_t k_stride, xgm_hit* hits, uint32_t* hit_ord, uint32_t* hit_collapse_ord,
-                                          uint32_t* hit_collapse_count, xgm_result_hdr* hdrs, uint64_t* collapsed_lower_bound) {
-    return sorted_batch_core(idx, qs, nq, sort, k_stride, hits, hit_ord, hdrs, -1, nullptr, 0, (int)collapse_slot, collapse_max, hit_collapse_ord,
-                             hit_collapse_count, collapsed_lower_bound);
-}
-
-/* ... every search with a ValueCountMatchSpy on spy_slot (include/xgm.h: xgm_search_sorted_spy_batch): counts [nq][n_counts] */
-extern "C" int xgm_search_sorted_spy_batch(xgm_index* idx, const xgm_query* qs, uint32_t nq, const xgm_sort_spec* sort, uint32_t k_stride, xgm_hit* hits,
-                                           uint32_t* hit_ord, xgm_result_hdr* hdrs, uint32_t spy_slot, uint32_t* counts, uint32_t n_counts) {
-    if (!counts) return xgm_set_error(XGM_E_INVALID, "null argument");
-    return sorted_batch_core(idx, qs, nq, sort, k_stride, hits, hit_ord, hdrs, (int)spy_slot, counts, n_counts);
-}
-
-extern "C" int xgm_search_sorted_spy(xgm_index* idx, const xgm_query* q, const xgm_sort_spec* sort, xgm_hit* hits, uint32_t* hit_ord,
-                                     xgm_result_hdr* hdr, uint32_t spy_slot, uint32_t* counts, uint32_t n_counts) {
-    return sorted_core(idx, q, sort, hits, hit_ord, hdr, (int)spy_slot, counts, n_counts);
+/* ... under Enquire::set_collapse_key(collapse_slot, collapse_max) (include/xgm.h: xgm_search_collapsed, xgm_search_collapsed_batch) */
+static SortedOpts collapse_opts(uint32_t collapse_slot, uint32_t collapse_max, uint32_t* hit_collapse_ord, uint32_t* hit_collapse_count, uint64_t* collapsed_lower_bound) {
+    SortedOpts o;
+    o.collapse_slot = (int)collapse_slot; o.cmax = collapse_max;
+    o.hit_cord = hit_collapse_ord; o.hit_ccount = hit_collapse_count; o.collapsed_lb = collapsed_lower_bound;
+    return o;
 }
 
 extern "C" int xgm_search_collapsed(xgm_index* idx, const xgm_query* q, const xgm_sort_spec* sort, uint32_t collapse_slot, uint32_t collapse_max,
                                     xgm_hit* hits, uint32_t* hit_ord, uint32_t* hit_collapse_ord, uint32_t* hit_collapse_count, xgm_result_hdr* hdr,
                                     uint64_t* collapsed_lower_bound) {
-    return sorted_core(idx, q, sort, hits, hit_ord, hdr, -1, nullptr, 0, (int)collapse_slot, collapse_max, hit_collapse_ord, hit_collapse_count, collapsed_lower_bound);
+    SortedOpts o = collapse_opts(collapse_slot, collapse_max, hit_collapse_ord, hit_collapse_count, collapsed_lower_bound);
+    o.single = true;
+    return sorted_batch_core(idx, q, 1, sort, 0, hits, hit_ord, hdr, o);
+}
+
+extern "C" int xgm_search_collapsed_batch(xgm_index* idx, const xgm_query* qs, uint32_t nq, const xgm_sort_spec* sort, uint32_t collapse_slot,
+                                          uint32_t collapse_max, uint32_t k_stride, xgm_hit* hits, uint32_t* hit_ord, uint32_t* hit_collapse_ord,
+                                          uint32_t* hit_collapse_count, xgm_result_hdr* hdrs, uint64_t* collapsed_lower_bound) {
+    return sorted_batch_core(idx, qs, nq, sort, k_stride, hits, hit_ord, hdrs, collapse_opts(collapse_slot, collapse_max, hit_collapse_ord, hit_collapse_count, collapsed_lower_bound));
+}
+
+/* ... with a ValueCountMatchSpy on spy_slot (include/xgm.h: xgm_search_sorted_spy, xgm_search_sorted_spy_batch: counts [nq][n_counts]); a slot below
+ * 0 — the filtered searches' "no spy" — leaves the options as they are */
+static SortedOpts spy_opts(int32_t spy_slot, uint32_t* counts, uint32_t n_counts) {
+    SortedOpts o;
+    if (spy_slot >= 0) { o.spy_slot = (int)spy_slot; o.counts = counts; o.n_counts = n_counts; }
+    return o;
+}
+
+extern "C" int xgm_search_sorted_spy(xgm_index* idx, const xgm_query* q, const xgm_sort_spec* sort, xgm_hit* hits, uint32_t* hit_ord,
+                                     xgm_result_hdr* hdr, uint32_t spy_slot, uint32_t* counts, uint32_t n_counts) {
+    SortedOpts o = spy_opts((int32_t)spy_slot, counts, n_counts);
+    o.single = true;
+    return sorted_batch_core(idx, q, 1, sort, 0, hits, hit_ord, hdr, o);
+}
+
+extern "C" int xgm_search_sorted_spy_batch(xgm_index* idx, const xgm_query* qs, uint32_t nq, const xgm_sort_spec* sort, uint32_t k_stride, xgm_hit* hits,
+                                           uint32_t* hit_ord, xgm_result_hdr* hdrs, uint32_t spy_slot, uint32_t* counts, uint32_t n_counts) {
+    if (!counts) return xgm_set_error(XGM_E_INVALID, "null argument");
+    return sorted_batch_core(idx, qs, nq, sort, k_stride, hits, hit_ord, hdrs, spy_opts((int32_t)spy_slot, counts, n_counts));
 }
 
 /* ---- value-range filters (include/xgm.h: xgm_filter_build, xgm_search_filtered) ---------------------------------------------
@@ -2153,6 +2113,46 @@ extern "C" int xgm_column_ord_range(const char* column_path, const char* begin, 
     return XGM_OK;
 }
 
+/* What every producer of a filter does around its kernel — xgm_filter_build, xgm_filter_build_query, xgm_filter_combine: a scratch of the pool, the
+ * counter, the bitmap, the event pair under xgm_index_set_profiling (tools/filter_time.py, tools/filter_query_time.py), one copy back, the filter.  launch(d_bits, n_padded, d_count, stream) enqueues the kernel. */
+template <class Launch>
+static int filter_produce(xgm_index* idx, const char* kernel_name, Launch&& launch, xgm_filter** out, uint64_t* n_docs) {
+    int rc = use_device(idx->device);
+    if (rc) return rc;
+    const uint64_t n_bits = (uint64_t)idx->hdr.lastdocid + 1u;
+    const uint32_t n_words = (uint32_t)((n_bits + 31u) / 32u);
+    const uint32_t n_padded = (uint32_t)(((uint64_t)n_words + XGM_FILTER_PAD_WORDS - 1u) / XGM_FILTER_PAD_WORDS * XGM_FILTER_PAD_WORDS);
+    XgmScratch* sc;
+    if ((rc = scratch_acquire(idx, &sc))) return rc;
+    ScratchRelease release_{idx, sc};
+    DeviceBuffers tmp;
+    unsigned long long* d_count = nullptr;
+    if ((rc = tmp.alloc((void**)&d_count, 8))) return rc;
+    uint32_t* d_bits = nullptr;
+    HIP_TRY(hipMalloc((void**)&d_bits, (size_t)n_padded * 4));
+    unsigned long long count = 0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;                             /* xgm_index_set_profiling: a pair around the kernel (tools/filter_query_time.py) */
+    if ((rc = next_event_pair(idx, &ev0, &ev1))) { hipFree(d_bits); return rc; }
+    hipError_t e = hipMemsetAsync(d_count, 0, 8, sc->stream);
+    if (e == hipSuccess) {
+        if (ev0) hipEventRecord(ev0, sc->stream);
+        rc = launch(d_bits, n_padded, d_count, sc->stream);
+        if (ev1) hipEventRecord(ev1, sc->stream);
+        if (rc) { hipStreamSynchronize(sc->stream); hipFree(d_bits); return rc; }
+        if (ev0) idx->last_kernel = kernel_name;
+        e = hipMemcpyAsync(&count, d_count, 8, hipMemcpyDeviceToHost, sc->stream);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(sc->stream);
+    if (e != hipSuccess) { hipStreamSynchronize(sc->stream); hipFree(d_bits); return xgm_launch_error(kernel_name, (int)e, hipGetErrorString(e)); }
+    xgm_filter* flt = new xgm_filter();
+    flt->device = idx->device; flt->lastdocid = idx->hdr.lastdocid;
+    flt->n_words = n_words; flt->n_words_padded = n_padded;
+    flt->d_bits = d_bits; flt->n_docs = count;
+    if (n_docs) *n_docs = count;
+    *out = flt;
+    return XGM_OK;
+}
+
 extern "C" int xgm_filter_build(xgm_index* idx, const xgm_value_range* ranges, uint32_t n_ranges, xgm_filter** out, uint64_t* n_docs) {
     if (!idx || !ranges || !out) return xgm_set_error(XGM_E_INVALID, "null argument");
     *out = nullptr;
@@ -2182,50 +2182,9 @@ extern "C" int xgm_filter_build(xgm_index* idx, const xgm_value_range* ranges, u
             cl.ord[c] = (const uint32_t*)it->second.first;
         }
     }
-    int rc = use_device(idx->device);
-    if (rc) return rc;
-    const uint64_t n_bits = (uint64_t)idx->hdr.lastdocid + 1u;
-    const uint32_t n_words = (uint32_t)((n_bits + 31u) / 32u);
-    const uint32_t n_padded = (uint32_t)(((uint64_t)n_words + XGM_FILTER_PAD_WORDS - 1u) / XGM_FILTER_PAD_WORDS * XGM_FILTER_PAD_WORDS);
-    XgmScratch* sc;
-    if ((rc = scratch_acquire(idx, &sc))) return rc;
-    ScratchRelease release_{idx, sc};
-    DeviceBuffers tmp;
-    unsigned long long* d_count = nullptr;
-    if ((rc = tmp.alloc((void**)&d_count, 8))) return rc;
-    uint32_t* d_bits = nullptr;
-    HIP_TRY(hipMalloc((void**)&d_bits, (size_t)n_padded * 4));
-    unsigned long long count = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;                             /* xgm_index_set_profiling: a pair around the mark kernel (tools/filter_time.py) */
-    if (idx->profiling) {
-        std::lock_guard<std::mutex> lk(idx->scratch_mu);
-        if (idx->prof_used == idx->prof_events.size()) {
-            hipEvent_t a = nullptr, b = nullptr;
-            if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { if (a) hipEventDestroy(a); hipFree(d_bits); return xgm_launch_error("filter build", 0, "hipEventCreate"); }
-            idx->prof_events.push_back({a, b});
-        }
-        ev0 = (hipEvent_t)idx->prof_events[idx->prof_used].first;
-        ev1 = (hipEvent_t)idx->prof_events[idx->prof_used].second;
-        ++idx->prof_used;
-    }
-    hipError_t e = hipMemsetAsync(d_count, 0, 8, sc->stream);
-    if (e == hipSuccess) {
-        if (ev0) hipEventRecord(ev0, sc->stream);
-        rc = xgm_launch_filter_mark(cl, idx->hdr.lastdocid, n_padded, d_bits, d_count, sc->stream);
-        if (ev1) hipEventRecord(ev1, sc->stream);
-        if (rc) { hipStreamSynchronize(sc->stream); hipFree(d_bits); return rc; }
-        if (ev0) idx->last_kernel = lists ? "xgm_filter_mark_lists_kernel" : "xgm_filter_mark_kernel";
-        e = hipMemcpyAsync(&count, d_count, 8, hipMemcpyDeviceToHost, sc->stream);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(sc->stream);
-    if (e != hipSuccess) { hipStreamSynchronize(sc->stream); hipFree(d_bits); return xgm_launch_error("filter build", (int)e, hipGetErrorString(e)); }
-    xgm_filter* flt = new xgm_filter();
-    flt->device = idx->device; flt->lastdocid = idx->hdr.lastdocid;
-    flt->n_words = n_words; flt->n_words_padded = n_padded;
-    flt->d_bits = d_bits; flt->n_docs = count;
-    if (n_docs) *n_docs = count;
-    *out = flt;
-    return XGM_OK;
+    return filter_produce(idx, lists ? "xgm_filter_mark_lists_kernel" : "xgm_filter_mark_kernel", [&](uint32_t* d_bits, uint32_t n_padded, unsigned long long* d_count, hipStream_t stream) {
+        return xgm_launch_filter_mark(cl, idx->hdr.lastdocid, n_padded, d_bits, d_count, stream);
+    }, out, n_docs);
 }
 
 extern "C" int xgm_filter_read(const xgm_filter* flt, uint32_t* words, uint32_t n_words) {
@@ -2331,56 +2290,6 @@ static int filter_program_of(const xgm_index* idx, const xgm_query* q, xgm_filte
     return XGM_OK;
 }
 
-/* What xgm_filter_build does around its kernel, for the two producers below: a scratch of the pool, the counter, the bitmap, the event pair
- * under xgm_index_set_profiling, one copy back, the filter.  launch(d_bits, n_padded, d_count, stream) enqueues the kernel. */
-template <class Launch>
-static int filter_produce(xgm_index* idx, const char* kernel_name, Launch&& launch, xgm_filter** out, uint64_t* n_docs) {
-    int rc = use_device(idx->device);
-    if (rc) return rc;
-    const uint64_t n_bits = (uint64_t)idx->hdr.lastdocid + 1u;
-    const uint32_t n_words = (uint32_t)((n_bits + 31u) / 32u);
-    const uint32_t n_padded = (uint32_t)(((uint64_t)n_words + XGM_FILTER_PAD_WORDS - 1u) / XGM_FILTER_PAD_WORDS * XGM_FILTER_PAD_WORDS);
-    XgmScratch* sc;
-    if ((rc = scratch_acquire(idx, &sc))) return rc;
-    ScratchRelease release_{idx, sc};
-    DeviceBuffers tmp;
-    unsigned long long* d_count = nullptr;
-    if ((rc = tmp.alloc((void**)&d_count, 8))) return rc;
-    uint32_t* d_bits = nullptr;
-    HIP_TRY(hipMalloc((void**)&d_bits, (size_t)n_padded * 4));
-    unsigned long long count = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;                             /* xgm_index_set_profiling: a pair around the kernel (tools/filter_query_time.py) */
-    if (idx->profiling) {
-        std::lock_guard<std::mutex> lk(idx->scratch_mu);
-        if (idx->prof_used == idx->prof_events.size()) {
-            hipEvent_t a = nullptr, b = nullptr;
-            if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { if (a) hipEventDestroy(a); hipFree(d_bits); return xgm_launch_error(kernel_name, 0, "hipEventCreate"); }
-            idx->prof_events.push_back({a, b});
-        }
-        ev0 = (hipEvent_t)idx->prof_events[idx->prof_used].first;
-        ev1 = (hipEvent_t)idx->prof_events[idx->prof_used].second;
-        ++idx->prof_used;
-    }
-    hipError_t e = hipMemsetAsync(d_count, 0, 8, sc->stream);
-    if (e == hipSuccess) {
-        if (ev0) hipEventRecord(ev0, sc->stream);
-        rc = launch(d_bits, n_padded, d_count, sc->stream);
-        if (ev1) hipEventRecord(ev1, sc->stream);
-        if (rc) { hipStreamSynchronize(sc->stream); hipFree(d_bits); return rc; }
-        if (ev0) idx->last_kernel = kernel_name;
-        e = hipMemcpyAsync(&count, d_count, 8, hipMemcpyDeviceToHost, sc->stream);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(sc->stream);
-    if (e != hipSuccess) { hipStreamSynchronize(sc->stream); hipFree(d_bits); return xgm_launch_error(kernel_name, (int)e, hipGetErrorString(e)); }
-    xgm_filter* flt = new xgm_filter();
-    flt->device = idx->device; flt->lastdocid = idx->hdr.lastdocid;
-    flt->n_words = n_words; flt->n_words_padded = n_padded;
-    flt->d_bits = d_bits; flt->n_docs = count;
-    if (n_docs) *n_docs = count;
-    *out = flt;
-    return XGM_OK;
-}
-
 extern "C" int xgm_filter_build_query(xgm_index* idx, const xgm_query* plan, xgm_filter** out, uint64_t* n_docs) {
     if (!idx || !plan || !out) return xgm_set_error(XGM_E_INVALID, "null argument");
     *out = nullptr;
@@ -2407,16 +2316,18 @@ extern "C" int xgm_filter_combine(xgm_index* idx, uint32_t op, const xgm_filter*
 extern "C" int xgm_search_filtered(xgm_index* idx, const xgm_query* q, const xgm_filter* flt, const xgm_sort_spec* sort, xgm_hit* hits, uint32_t* hit_ord,
                                    xgm_result_hdr* hdr, int32_t spy_slot, uint32_t* counts, uint32_t n_counts) {
     if (!flt) return xgm_set_error(XGM_E_INVALID, "null argument");
-    const bool spy = spy_slot >= 0;
-    return sorted_core(idx, q, sort, hits, hit_ord, hdr, spy ? (int)spy_slot : -1, spy ? counts : nullptr, spy ? n_counts : 0u, -1, 0, nullptr, nullptr, nullptr, flt);
+    SortedOpts o = spy_opts(spy_slot, counts, n_counts);
+    o.flt = flt;
+    o.single = true;
+    return sorted_batch_core(idx, q, 1, sort, 0, hits, hit_ord, hdr, o);
 }
 
 extern "C" int xgm_search_filtered_batch(xgm_index* idx, const xgm_query* qs, uint32_t nq, const xgm_filter* flt, const xgm_sort_spec* sort, uint32_t k_stride,
                                          xgm_hit* hits, uint32_t* hit_ord, xgm_result_hdr* hdrs, int32_t spy_slot, uint32_t* counts, uint32_t n_counts) {
     if (!flt) return xgm_set_error(XGM_E_INVALID, "null argument");
-    const bool spy = spy_slot >= 0;
-    return sorted_batch_core(idx, qs, nq, sort, k_stride, hits, hit_ord, hdrs, spy ? (int)spy_slot : -1, spy ? counts : nullptr, spy ? n_counts : 0u, -1, 0, nullptr, nullptr,
-                             nullptr, flt);
+    SortedOpts o = spy_opts(spy_slot, counts, n_counts);
+    o.flt = flt;
+    return sorted_batch_core(idx, qs, nq, sort, k_stride, hits, hit_ord, hdrs, o);
 }
 
 /* ---- a filter as the whole query (include/xgm.h: xgm_search_range) ---------------------------------------------------------------
@@ -2431,22 +2342,17 @@ extern "C" int xgm_search_range(xgm_index* idx, const xgm_filter* flt, const xgm
     if (int frc = filter_usable(idx, flt)) return frc;
     if (sort && (sort->sort_by < XGM_SORT_VALUE || sort->sort_by > XGM_SORT_RELEVANCE_VALUE)) return xgm_set_error(XGM_E_INVALID, "sort_by %u", sort->sort_by);
     xgm_range_launch L = {};
-    {
-        std::lock_guard<std::mutex> lk(idx->columns_mu);
-        if (sort) {
-            auto it = idx->columns.find(sort->slot);
-            if (it == idx->columns.end()) return XGM_UNSUPPORTED;
-            L.ord = (const uint32_t*)it->second.first;
-            L.n_distinct = it->second.second;
-            L.reverse = sort->reverse ? 1u : 0u;
-        }
-        if (spy_slot >= 0) {
-            auto it = idx->columns.find((uint32_t)spy_slot);
-            if (it == idx->columns.end()) return XGM_UNSUPPORTED;
-            if (!counts || n_counts != it->second.second + 1u) return xgm_set_error(XGM_E_INVALID, "spy: %u counters for a column of %u distinct values (+ 1 for no value)", n_counts, it->second.second);
-            L.spy_ord = (const uint32_t*)it->second.first;
-            L.n_counts = n_counts;
-        }
+    ColumnRef col;
+    if (sort) {
+        if (!find_column(idx, sort->slot, &col)) return XGM_UNSUPPORTED;
+        L.ord = col.ord;
+        L.n_distinct = col.n_distinct;
+        L.reverse = sort->reverse ? 1u : 0u;
+    }
+    if (spy_slot >= 0) {
+        if (int src = find_spy_column(idx, (uint32_t)spy_slot, counts, n_counts, &col)) return src;
+        L.spy_ord = col.ord;
+        L.n_counts = n_counts;
     }
     memset(hdr, 0, sizeof *hdr);
     hdr->matches_exact = flt->n_docs;
@@ -2469,18 +2375,7 @@ extern "C" int xgm_search_range(xgm_index* idx, const xgm_filter* flt, const xgm
     if ((rc = grow(&sc->d_sorted, &sc->cap_sorted, y.total))) return rc;
     if ((rc = grow_pinned(&sc->h_sorted, &sc->cap_hsorted, down))) return rc;
     L.work = sc->d_sorted;
-    if (idx->profiling) {
-        std::lock_guard<std::mutex> lk(idx->scratch_mu);
-        if (idx->prof_used == idx->prof_events.size()) {
-            hipEvent_t a, b;
-            HIP_TRY(hipEventCreate(&a));
-            HIP_TRY(hipEventCreate(&b));
-            idx->prof_events.push_back({a, b});
-        }
-        L.ev_start = (hipEvent_t)idx->prof_events[idx->prof_used].first;
-        L.ev_stop = (hipEvent_t)idx->prof_events[idx->prof_used].second;
-        ++idx->prof_used;
-    }
+    if ((rc = next_event_pair(idx, &L.ev_start, &L.ev_stop))) return rc;
     idx->last_kernel = "xgm_range_place_kernel";
     if ((rc = xgm_launch_range(L, sc->stream))) return rc;
     unsigned char* hb = (unsigned char*)sc->h_sorted;
@@ -2522,16 +2417,13 @@ extern "C" int xgm_filter_count_pairs(xgm_index* idx, const xgm_filter* flt, uin
     if (idx->device == XGM_DEVICE_NONE) return xgm_set_error(XGM_E_NO_DEVICE, "index opened without a device");
     if (int frc = filter_usable(idx, flt)) return frc;
     xgm_pairs_launch L = {};
-    {
-        std::lock_guard<std::mutex> lk(idx->columns_mu);
-        auto ia = idx->columns.find(slot_a), ib = idx->columns.find(slot_b);
-        if (ia == idx->columns.end() || ib == idx->columns.end())
-            return xgm_set_error(XGM_UNSUPPORTED, "pair counts: slot %u has no plain column attached", ia == idx->columns.end() ? slot_a : slot_b);
-        if (ia->second.second == 0xFFFFFFFFu || ib->second.second == 0xFFFFFFFFu)                             /* (the table's empty marker would be a pair) */
-            return xgm_set_error(XGM_UNSUPPORTED, "pair counts: the column of slot %u has n_distinct 0xFFFFFFFF", ia->second.second == 0xFFFFFFFFu ? slot_a : slot_b);
-        L.ord_a = (const uint32_t*)ia->second.first; L.n_a = ia->second.second;
-        L.ord_b = (const uint32_t*)ib->second.first; L.n_b = ib->second.second;
-    }
+    ColumnRef ca, cb;
+    const bool has_a = find_column(idx, slot_a, &ca), has_b = find_column(idx, slot_b, &cb);
+    if (!has_a || !has_b) return xgm_set_error(XGM_UNSUPPORTED, "pair counts: slot %u has no plain column attached", !has_a ? slot_a : slot_b);
+    if (ca.n_distinct == 0xFFFFFFFFu || cb.n_distinct == 0xFFFFFFFFu)                                       /* (the table's empty marker would be a pair) */
+        return xgm_set_error(XGM_UNSUPPORTED, "pair counts: the column of slot %u has n_distinct 0xFFFFFFFF", ca.n_distinct == 0xFFFFFFFFu ? slot_a : slot_b);
+    L.ord_a = ca.ord; L.n_a = ca.n_distinct;
+    L.ord_b = cb.ord; L.n_b = cb.n_distinct;
     if (flt->n_docs == 0) return XGM_OK;                           /* nothing passes: no pair, no launch */
     const uint64_t P = ((uint64_t)L.n_a + 1u) * ((uint64_t)L.n_b + 1u);          /* < 2^64: both factors are below 2^32 */
     const uint64_t most = std::min<uint64_t>(flt->n_docs, P);      /* distinct pairs there can be */
@@ -2568,18 +2460,7 @@ extern "C" int xgm_filter_count_pairs(xgm_index* idx, const xgm_filter* flt, uin
     if ((rc = grow_pinned(&sc->h_sorted, &sc->cap_hsorted, std::min<size_t>(kPairCopyBytes, std::max<size_t>((size_t)L.n_out * sizeof(xgm_pair_count), 256))))) return rc;
     L.work = sc->d_all;
     L.out = (xgm_pair_count*)(sc->d_all + y.total);
-    if (idx->profiling) {
-        std::lock_guard<std::mutex> lk(idx->scratch_mu);
-        if (idx->prof_used == idx->prof_events.size()) {
-            hipEvent_t a, b;
-            HIP_TRY(hipEventCreate(&a));
-            HIP_TRY(hipEventCreate(&b));
-            idx->prof_events.push_back({a, b});
-        }
-        L.ev_start = (hipEvent_t)idx->prof_events[idx->prof_used].first;
-        L.ev_stop = (hipEvent_t)idx->prof_events[idx->prof_used].second;
-        ++idx->prof_used;
-    }
+    if ((rc = next_event_pair(idx, &L.ev_start, &L.ev_stop))) return rc;
     idx->last_kernel = "xgm_pairs_tally_kernel";
     if ((rc = xgm_launch_pairs(L, sc->stream))) return rc;
     uint32_t* hw = (uint32_t*)sc->h_sorted;                        /* [0] distinct pairs, [1] the error word */
@@ -2621,68 +2502,37 @@ static int search_all_device(xgm_index* idx, const xgm_query* q, XgmScratch* sc,
     xgm_query q1 = *q;
     q1.first = 0; q1.maxitems = 1; q1.check_at_least = 0xFFFFFFFFu;          /* the kernel's own top-k is not used: keep it smallest; positions of every candidate tested */
     xgm_dev_query dq;
-    uint32_t kq = 0;
-    double mp = 0;
     BatchPlan bp;
-    if ((rc = plan_batch(idx, &q1, 1, &dq, &kq, &mp, &bp, true))) return rc;
-    if (bp.andw || bp.orw || bp.and_only || bp.cap > 8u * XGM_WG) return XGM_UNSUPPORTED;
-    if (xgm_match_sorted_smem_bytes(idx->hdr.stripe_bits - bp.sub_bits, bp.tab_terms, bp.phrase, bp.cap, bp.wide, bp.stripes_per_group) > 160u * 1024u) return XGM_UNSUPPORTED;
+    if ((rc = plan_sorted(idx, &q1, 1, UINT32_MAX, &dq, &bp))) return rc;
     dq.flags &= ~XGM_QF_POSPRUNE;
     if (list_conj && (dq.flags & XGM_QF_PHRASE)) dq.flags |= XGM_QF_LIST_CONJ;
-    const uint32_t n_work = bp.n_work;
     hipStream_t stream = sc->stream;
-    /* the sorted kernel's own buffers: [query | work list] up, [unit headers | unit candidates (k = 1)] */
-    const size_t o_q = 0, b_q = (sizeof dq + 15) & ~(size_t)15;
-    const size_t o_wk = o_q + b_q, b_wk = ((size_t)n_work * sizeof(xgm_work) + 15) & ~(size_t)15;
-    const size_t up_bytes = o_wk + b_wk;
-    const size_t o_gh = up_bytes, b_gh = (size_t)n_work * sizeof(xgm_group_hdr);
-    const size_t o_cd = o_gh + b_gh, b_cd = (size_t)n_work * sizeof(xgm_cand_sorted);
-    const size_t total = o_cd + b_cd;
-    if ((rc = grow(&sc->d_sorted, &sc->cap_sorted, total))) return rc;
-    if ((rc = grow_pinned(&sc->h_sorted, &sc->cap_hsorted, total + 16))) return rc;
     /* the list: [counter 16 B | keys | weights | hits | the ordering's bitmap and prefix counts | the caller's extra bytes] */
     const size_t tmp_bytes = xgm_all_order_bytes(idx->hdr.lastdocid);
     const size_t a_cnt = 0, a_k0 = 16, a_v0 = a_k0 + cap_dev * 8, a_hit = a_v0 + cap_dev * 8;
     const size_t a_tmp = (a_hit + cap_dev * sizeof(xgm_hit) + 255) & ~(size_t)255, a_ext = (a_tmp + tmp_bytes + 255) & ~(size_t)255, a_total = a_ext + extra_bytes;
+    /* the sorted kernel's own buffers (unit candidates: k = 1), 16 bytes more on the host for the list's counter */
+    SortedStage st;
+    if ((rc = stage_sorted(idx, sc, &dq, 1, bp, 1, 0, 16, &st))) return rc;
     if ((rc = grow(&sc->d_all, &sc->cap_all, a_total))) return rc;
     if (d_extra) *d_extra = sc->d_all + a_ext;
-    unsigned char* hb = (unsigned char*)sc->h_sorted;
-    memcpy(hb + o_q, &dq, sizeof dq);
-    memcpy(hb + o_wk, bp.work.data(), (size_t)n_work * sizeof(xgm_work));
-    HIP_TRY(hipMemcpyAsync(sc->d_sorted, hb, up_bytes, hipMemcpyHostToDevice, stream));
     HIP_TRY(hipMemsetAsync(sc->d_all + a_cnt, 0, 16, stream));
-    xgm_match_launch L;
-    L.seg = idx->view;
-    L.queries = (xgm_dev_query*)(sc->d_sorted + o_q);
-    L.nq = 1; L.n_work = n_work; L.work = (xgm_work*)(sc->d_sorted + o_wk); L.stripes_per_group = bp.stripes_per_group; L.sub_bits = bp.sub_bits;
-    L.tab_terms = bp.tab_terms; L.cap = bp.cap; L.k_stride = 1;
-    L.phrase = bp.phrase; L.wide = bp.wide; L.sided = 0;
-    L.cand = nullptr; L.ghdr = (xgm_group_hdr*)(sc->d_sorted + o_gh);
     unsigned long long* d_cnt = (unsigned long long*)(sc->d_all + a_cnt);
     unsigned long long* k0 = (unsigned long long*)(sc->d_all + a_k0);
     unsigned long long* v0 = (unsigned long long*)(sc->d_all + a_v0);
-    idx->last_kernel = "xgm_match_sorted_kernel";
-    if ((rc = xgm_launch_match_sorted(L, nullptr, 4u, 0u, nullptr, nullptr, nullptr, 0u, (xgm_cand_sorted*)(sc->d_sorted + o_cd), stream, k0, v0, d_cnt, cap_dev))) return rc;
-    unsigned long long* h_cnt = (unsigned long long*)(hb + total);
-    HIP_TRY(hipMemcpyAsync(hb + o_gh, sc->d_sorted + o_gh, b_gh, hipMemcpyDeviceToHost, stream));
+    if ((rc = xgm_launch_match_sorted(st.L, nullptr, 4u, 0u, nullptr, nullptr, nullptr, 0u, st.d_cand, stream, k0, v0, d_cnt, cap_dev))) return rc;
+    unsigned long long* h_cnt = (unsigned long long*)(st.hb + st.total);
+    HIP_TRY(hipMemcpyAsync(st.hb + st.o_gh, sc->d_sorted + st.o_gh, st.o_cd - st.o_gh, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipMemcpyAsync(h_cnt, d_cnt, 8, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     const uint64_t n = *h_cnt;
     /* the whole match's count and best weight from the unit headers (the same fields xgm_search_sorted reports) */
-    const xgm_group_hdr* gh = (const xgm_group_hdr*)(hb + o_gh);
-    uint64_t matches = 0, max_w = 0;
-    uint32_t max_d = UINT32_MAX, max_m = 0;
-    for (uint32_t u = 0; u < n_work; ++u) {
-        const xgm_group_hdr& g = gh[u];
-        matches += g.matches;
-        if (g.c_pad[0] != UINT32_MAX && (max_d == UINT32_MAX || g.c_pos > max_w || (g.c_pos == max_w && g.c_pad[0] < max_d))) { max_w = g.c_pos; max_d = g.c_pad[0]; max_m = g.c_pad[1]; }
-    }
+    UnitFold fold;
+    fold.add((const xgm_group_hdr*)(st.hb + st.o_gh), 0, bp.n_work);
+    const uint64_t matches = fold.matches;
     if ((dq.flags & XGM_QF_LIST_CONJ) ? matches > n : matches != n)
         return xgm_set_error(XGM_E_DEVICE, "xgm_search_all: %llu documents listed, %llu counted", (unsigned long long)n, (unsigned long long)matches);
-    memset(hdr, 0, sizeof *hdr);
-    hdr->matches_exact = matches;
-    hdr->max_possible = q->max_possible;
-    if (max_d != UINT32_MAX) { memcpy(&hdr->max_attained, &max_w, 8); hdr->max_weight_subqs_matched = max_m; }
+    fold.write(hdr, q->max_possible);
     *n_list = n; *n_matches = matches;
     if (n > cap_dev || n == 0) return XGM_OK;                       /* does not fit (the caller decides what that means) / nothing to order */
     xgm_hit* d_out = (xgm_hit*)(sc->d_all + a_hit);
