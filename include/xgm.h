@@ -604,23 +604,76 @@ void xgm_filter_free(xgm_filter*);
  * XGM_E_INVALID: a null idx / plan / out, a plan that is not well formed (a term id beyond the dictionary, masks or tree operands out of
  * range); XGM_E_NO_DEVICE: an index without a device; XGM_UNSUPPORTED: an ACTIVE positional plan (PHRASE / NEAR with phrase_active), a tree
  * that reuses a node so often that its expansion exceeds the kernel's program.
- * NOT offered: positional plans; a complement or Query::MatchAll (which documents EXIST is another question); several plans in one launch;
- * shards; xgm_mset_bounds* of a search under such a filter.  The matcher hook does not lower to this call yet.
+ * NOT offered: positional plans; several plans in one launch; shards; xgm_mset_bounds* of a search under such a filter.  (Which documents EXIST
+ * is another producer's question: xgm_filter_all, and XGM_FILTER_NOT of xgm_filter_combine for a complement.)  The matcher hook does not lower to
+ * this call yet.
  * Replaces: OP_FILTER's boolean right-hand side and Query(OP_SCALE_WEIGHT, q, 0) as the matcher walks them per candidate
  * (matcher/matcher.cc:482-536); for `_range`, the accuracy-term side of OP_FILTER(MultipleValue*, terms). */
 int xgm_filter_build_query(xgm_index*, const xgm_query* plan, xgm_filter** out, uint64_t* n_docs /* may be NULL */);
 
-/* A new filter from two filters of the same index and lastdocid: a & b, a | b or a & ~b, word by word on the device; a and b stay as they are
- * (a == b is allowed), *n_docs (may be NULL) = the documents of the result.  DSL `_and` / `_or` / `_not` BETWEEN restrictions: two ranges
- * OR-ed, a range minus a term, a clause filter AND a query filter.  Synchronous; safe from any number of threads.
- * XGM_E_INVALID: a null idx / a / b / out, an op outside 1 .. 3, a filter of another device or lastdocid; XGM_E_NO_DEVICE: an index without
- * a device.
- * NOT offered: a complement (NOT b alone) and Query::MatchAll — AND_NOT needs a left side; more than two operands in one call.
- * Replaces: MultiAndPostList / OrPostList / AndNotPostList over unweighted sub-trees under OP_FILTER (matcher/matcher.cc:482-536). */
+/* A new filter from two filters of the same index and lastdocid: a & b, a | b, a & ~b or a ^ b, word by word on the device; a and b stay as they
+ * are (a == b is allowed), *n_docs (may be NULL) = the documents of the result.  DSL `_and` / `_or` / `_not` / `_xor` BETWEEN restrictions: two
+ * ranges OR-ed, a range minus a term, a clause filter AND a query filter.  Synchronous; safe from any number of threads.
+ * XGM_FILTER_NOT is the complement, the DSL's bare `_not` — Query(OP_AND_NOT, MatchAll, q): live & ~a, where `live` is the index's live set
+ * (xgm_filter_all below), so a deleted docid, docid 0 and the docids beyond lastdocid stay clear.  b must be NULL.  NOT of the empty filter is the
+ * all-filter, NOT of the all-filter is empty with *n_docs 0.  XGM_FILTER_XOR needs no live set: a ^ b lies inside a | b.
+ * XGM_E_INVALID: a null idx / a / out, a null b for any op but NOT, a non-null b for NOT, an op outside 1 .. 5, a filter of another device or
+ * lastdocid; XGM_E_NO_DEVICE: an index without a device; XGM_UNSUPPORTED (XGM_FILTER_NOT only): the index cannot tell its live documents from its
+ * deleted ones and no live set is attached — see xgm_filter_all; the text of xgm_last_error names xgm_index_attach_live.
+ * NOT offered: more than two operands in one call; positional plans as operands, several plans per launch, shards and xgm_mset_bounds* (the filters'
+ * own limits); MatchAll or a complement as a WEIGHTED subquery inside an AND / OR tree of xgm_plan_query — these are filters, they weigh nothing.
+ * Replaces: MultiAndPostList / OrPostList / AndNotPostList (and OP_XOR's postlist) over unweighted sub-trees under OP_FILTER
+ * (matcher/matcher.cc:482-536); for XGM_FILTER_NOT, AndNotPostList (matcher/andnotpostlist.cc) whose left side is the doclen-list postlist the matcher
+ * opens for the empty term (LocalSubMatch::open_post_list, matcher/localsubmatch.cc:232 → GlassAllDocsPostList, backends/glass/glass_database.cc:867-873). */
 #define XGM_FILTER_AND     1u   /* a & b  */
 #define XGM_FILTER_OR      2u   /* a | b  */
 #define XGM_FILTER_AND_NOT 3u   /* a & ~b */
+#define XGM_FILTER_NOT     4u   /* live & ~a; b == NULL */
+#define XGM_FILTER_XOR     5u   /* a ^ b  */
 int xgm_filter_combine(xgm_index*, uint32_t op, const xgm_filter* a, const xgm_filter* b, xgm_filter** out, uint64_t* n_docs /* may be NULL */);
+
+/* The third producer: Query::MatchAll — Xapian::Query(std::string()), what Xapiand sends for an empty search, for an unbounded range
+ * (reference src/multivalue/range.cc:305, generate_terms.cc) and to browse (src/server/http_client.cc:2862) — as a filter: the index's LIVE SET,
+ * one bit per docid that exists.  *out is a new, ordinary xgm_filter with xgm_filter_build's contract: padded, every word written, bit 0 and the bits
+ * beyond lastdocid clear, immutable, bound to the index's lastdocid, usable from any thread by xgm_search_filtered*, xgm_search_range,
+ * xgm_filter_count_pairs and xgm_filter_combine; it owns its own device copy and is freed by xgm_filter_free independently of the index.
+ * *n_docs (may be NULL) = the index's doccount.  Synchronous; safe from any number of threads on one index.
+ *   MatchAll as the whole query     xgm_filter_all + xgm_search_range: the first k live docids in ascending order (or under a value sort, with a spy),
+ *                                   weights +0.0 — the reference's answer, every weight of the tree being 0 (matcher/matcher.cc:415-430)
+ *   AND_NOT(MatchAll, q), `_not`    xgm_filter_combine(XGM_FILTER_NOT) of q's filter
+ * The index makes its live set on the first call that needs one (this call or XGM_FILTER_NOT) and keeps it until xgm_index_close; concurrent first
+ * calls make it once.  It comes from the first of these that applies, and it is EXACT or the call declines:
+ *   (a) doccount == lastdocid: no gaps, every docid 1 .. lastdocid is live, whatever its length;
+ *   (b) a live set attached by xgm_index_attach_live / _file: used as attached;
+ *   (c) the document lengths: a kernel marks doclen[d] != 0 (40 MB in, 1.25 MB out at 10 M documents) and counts the marks.  A length of 0 means
+ *       "deleted or never added" — and is also the length of a live document whose terms are all boolean (wdf 0 adds nothing to the length: Xapiand's
+ *       keyword-only documents).  When the count equals doccount no live document has length 0 and the bits are exact; otherwise the lengths cannot
+ *       tell the two apart and this call and XGM_FILTER_NOT return XGM_UNSUPPORTED, now and on every later call, until a live set is attached.
+ * XGM_E_INVALID: a null idx / out; XGM_E_NO_DEVICE: an index without a device; XGM_UNSUPPORTED: rule (c) declined (xgm_last_error names
+ * xgm_index_attach_live).
+ * NOT offered: MatchAll as a weighted subquery inside an AND / OR tree (xgm_plan_query declines an empty term as before: combine its filter with
+ * xgm_search_filtered instead); positional plans, several plans per launch, shards and xgm_mset_bounds* as for every filter.
+ * Replaces: the postlist over the doclen list that the matcher opens for an empty term (GlassAllDocsPostList, backends/glass/glass_alldocspostlist.cc,
+ * made by GlassDatabase::open_post_list for term.empty(), glass_database.cc:867-873, for LocalSubMatch::open_post_list, matcher/localsubmatch.cc:232)
+ * walked by the main loop (matcher/matcher.cc:482-536). */
+int xgm_filter_all(xgm_index*, xgm_filter** out, uint64_t* n_docs /* may be NULL */);
+
+/* Attach a shard's live set from host memory, for shards with deletions AND documents of length 0: bit d & 31 of words[d >> 5] set when docid d
+ * exists, n_words = ceil((lastdocid + 1) / 32) — the layout of xgm_filter_read.  The hook exports and attaches it on commit when doccount != lastdocid
+ * (INTEGRATION.md 2).  Attach BEFORE the first xgm_filter_all / XGM_FILTER_NOT.
+ * XGM_E_INVALID: a null argument; another n_words; bit 0 set; a bit beyond lastdocid set; a popcount that is not the index's doccount; a second
+ * attach; an attach after the live set was built by rule (a) or (c) (after a DECLINE it is accepted: nothing was handed out).  XGM_E_NO_DEVICE: an
+ * index without a device.  The segment format does not change: the live set is a side file, as columns are. */
+int xgm_index_attach_live(xgm_index*, const uint32_t* words, uint32_t n_words);
+/* The live set of a committed glass shard as a file: a docid that appears in the shard's doclen list is live, whatever its length — the only source
+ * of truth (the list MatchAll walks in the reference).  "XGMLIV1\0", u32 lastdocid, u32 doccount, u32 n_words, u32 0, u32 words[n_words].  Host only.
+ * XGM_E_IO / XGM_E_INVALID as for xgm_glass_export_column; XGM_E_INVALID also when the list's documents are not the version file's doccount. */
+int xgm_glass_export_live(const char* glass_dir, const char* out_path);
+/* xgm_index_attach_live from such a file; a file written for another lastdocid or doccount (another revision) is XGM_E_INVALID. */
+int xgm_index_attach_live_file(xgm_index*, const char* path);
+/* Diagnostics: out4 = {0 no live set asked for yet / 1 held / 2 declined, its source (1 no gaps, 2 attached, 3 the lengths), launches of the marking
+ * kernel so far (never more than one), the documents of non-zero length it counted}. */
+int xgm_debug_live_info(xgm_index*, uint64_t* out4);
 
 /* xgm_search_sorted / xgm_search_sorted_spy for Query(OP_FILTER, q, range_1 AND ... AND range_n): the documents of q that the filter lets
  * through, under the given sort (sort == NULL: by relevance), with a ValueCountMatchSpy on spy_slot when spy_slot >= 0 (counts / n_counts
@@ -663,7 +716,7 @@ int xgm_search_filtered_batch(xgm_index*, const xgm_query* qs, uint32_t nq, cons
  * XGM_E_INVALID: a null idx / flt / hits / hdr, k == 0 or k > XGM_MAX_K, a filter built for another index, an n_counts that is not the
  * spy column's; XGM_UNSUPPORTED: the sort or spy slot has no column attached.  Safe from any number of threads on one index and one filter.
  * NOT offered: a collapse key; xgm_mset_bounds* (the reason given for xgm_search_filtered); descending docid order (set_docid_order); a batch
- * form (one filter has one answer); shards; Query::MatchAll without a filter.  The matcher hook does not lower such queries yet.
+ * form (one filter has one answer); shards.  (Query::MatchAll is this call over xgm_filter_all.)  The matcher hook does not lower such queries yet.
  * Replaces: ValueRangePostList as the root of the posting-list tree walked by the matcher's main loop (matcher/matcher.cc:482-536). */
 int xgm_search_range(xgm_index*, const xgm_filter*, const xgm_sort_spec* sort /* NULL = docid order */,
                      uint32_t k /* first + maxitems, 1 .. XGM_MAX_K */,

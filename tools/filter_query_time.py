@@ -5,18 +5,26 @@
   or5                               OR of five
   or16                              OR of 16 terms (an accuracy-term set)
   combine                           xgm_filter_combine(AND) of the filters of term_r1 and term_r100
+  not, xor                          xgm_filter_combine(XGM_FILTER_NOT) of term_r1's filter; (XGM_FILTER_XOR) of the two: the same three bitmaps as combine
+  all                               xgm_filter_all with the index's live set cached: two bitmaps
+  all_first                         the ONE xgm_filter_all that makes the live set, on a freshly built (or opened) index: one sample per index,
+                                    --first-opens of them, every sample listed; XGM_LIVE_FROM_LENGTHS=1 makes an index without gaps — the synthetic one —
+                                    mark its set from the lengths (rule (c): the doclen section in, the bitmap out) instead of by rule (a) (the bitmap out)
+--rows a,b,... measures only those rows (an A/B of one row between two builds of the library).
 Per row: the median over --calls calls (after --warmup) of
   kernel_us   the hipEvent pair the call records around its kernel (xgm_index_set_profiling / xgm_last_kernel_ms, read after each call)
   wall_us     host clock around the whole call (allocation of the bitmap, launch, the count's copy back, a stream synchronise)
 beside
   bound_us    (1 KB per non-empty (container term, stripe) + 4 B per flat posting read + the padded bitmap's bytes written) at 8 TB/s; for combine
-              two bitmaps read and one written.  Which terms have containers is the library's rule (df >= 32 per stripe on average); their non-empty
+              two bitmaps read and one written, and so for not and xor; for all one read and one written; for all_first the doclen section (rule (c)
+              only) and the bitmap written, twice: the set, then the filter's copy.  Which terms have containers is the library's rule (df >= 32 per stripe on average); their non-empty
               stripes and the other terms' postings are counted from the terms' own match lists.
   parent_us   the only route to the same bits without this call: xgm_search_all of the same plan (for combine: of the AND of the two terms) into a
               buffer allocated once, plus setting the bits on the host with numpy; wall clock, median of --parent-calls calls after two.  null where
-              xgm_search_all declines the plan (XGM_UNSUPPORTED: the parent has no route to these bits at all).
+              xgm_search_all declines the plan (XGM_UNSUPPORTED: the parent has no route to these bits at all) and for all, all_first, not and xor (no
+              plan expresses them).
 Every row's set bits are checked against the parent route's before anything is timed (where it declines: against the union or intersection of its
-answers for the single terms).  --segment FILE measures an index opened from a segment file instead of the synthetic one (a rehearsal under the kernel
+answers for the single terms; all, not and xor: against numpy over the single terms' answers and every docid 1 .. lastdocid — the synthetic index has no gaps).  --segment FILE measures an index opened from a segment file instead of the synthetic one (a rehearsal under the kernel
 emulation: its times mean nothing).
 Prints one JSON line (and writes it to --out)."""
 import argparse
@@ -104,13 +112,20 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--parent-calls", type=int, default=20)
     ap.add_argument("--segment")
+    ap.add_argument("--rows", help="comma-separated row names (default: every row)")
+    ap.add_argument("--first-opens", type=int, default=5)
     ap.add_argument("--out")
     args = ap.parse_args()
     import torch
     emulated = not torch.cuda.is_available()                                   # a rehearsal against tests/emu: its times mean nothing
     if emulated and not __import__("os").environ.get("XGM_LIB_PATH"):
         sys.exit("filter_query_time.py measures on the GPU: none here")
-    db = Database(args.segment) if args.segment else Database.synthetic(CORPUS_SEED, args.docs, args.vocab, with_positions=False)
+    def open_index():
+        return Database(args.segment) if args.segment else Database.synthetic(CORPUS_SEED, args.docs, args.vocab, with_positions=False)
+    db = open_index()
+    names = [n for n, _, _ in ROWS] + ["combine", "not", "xor", "all", "all_first"]
+    wanted = set(args.rows.split(",")) if args.rows else set(names)
+    assert wanted <= set(names), sorted(wanted - set(names))
     last = db.get_lastdocid()
     n_stripes = (last >> 13) + 1
     n_words = (last + 32) // 32
@@ -127,6 +142,8 @@ def main():
         return 1024 * stripes if dense else 4 * df
     rows = {}
     for name, op, terms in ROWS:
+        if name not in wanted:
+            continue
         p = make_plan(db, op, terms)
         bound = round((sum(term_bytes(t) for t in terms) + bitmap_bytes) / HBM_BYTES_PER_S * 1e6, 3)
         has_parent = parent.supports(p)
@@ -139,13 +156,34 @@ def main():
         flt.close()
         rows[name]["build"] = (lambda p=p: db.build_query_filter(p))
         rows[name]["parent_plan"] = p
-    fa, fb = db.build_query_filter(rows["term_r1"]["parent_plan"]), db.build_query_filter(rows["term_r100"]["parent_plan"])
+    pa, pb = make_plan(db, "OR", ["t1"]), make_plan(db, "OR", ["t100"])
+    fa, fb = db.build_query_filter(pa), db.build_query_filter(pb)
     both = make_plan(db, "AND", ["t1", "t100"])
-    fc = fa.combine(fb, _lib.XGM_FILTER_AND)
-    assert (np.array(fc.words(), dtype=np.uint32) == parent.words(both)).all()
-    rows["combine"] = dict(terms=["t1", "t100"], op="filter AND filter", n_docs=fc.n_docs, kernel="xgm_filter_combine_kernel", has_parent=True,
-                           bound_us=round(3 * bitmap_bytes / HBM_BYTES_PER_S * 1e6, 3), build=(lambda: fa.combine(fb, _lib.XGM_FILTER_AND)), parent_plan=both)
-    fc.close()
+    if "combine" in wanted:
+        fc = fa.combine(fb, _lib.XGM_FILTER_AND)
+        assert (np.array(fc.words(), dtype=np.uint32) == parent.words(both)).all()
+        rows["combine"] = dict(terms=["t1", "t100"], op="filter AND filter", n_docs=fc.n_docs, kernel="xgm_filter_combine_kernel", has_parent=True,
+                               bound_us=round(3 * bitmap_bytes / HBM_BYTES_PER_S * 1e6, 3), build=(lambda: fa.combine(fb, _lib.XGM_FILTER_AND)), parent_plan=both)
+        fc.close()
+    # the rows without a parent route: numpy over the single terms' answers and the live set, which on an index without gaps is every docid 1 .. lastdocid
+    live = np.zeros((last + 32) // 32 * 32, dtype=np.uint8)
+    live[1:last + 1] = 1
+    live = np.packbits(live, bitorder="little").view("<u4")
+    if wanted & {"not", "xor", "all", "all_first"}:
+        assert args.segment or db.get_doccount() == last
+        wa, wb = parent.words(pa), parent.words(pb)
+        new = {"not": ("NOT filter", ["t1"], 3, lambda: fa.combine(None, _lib.XGM_FILTER_NOT), live & ~wa),
+               "xor": ("filter XOR filter", ["t1", "t100"], 3, lambda: fa.combine(fb, _lib.XGM_FILTER_XOR), wa ^ wb),
+               "all": ("MatchAll, the live set cached", [], 2, lambda: db.filter_all(), live)}
+        for name, (op, terms, n_maps, build, want) in new.items():
+            if name not in wanted:
+                continue
+            flt = build()
+            assert (np.array(flt.words(), dtype=np.uint32) == want).all() and flt.n_docs == int(np.unpackbits(want.view(np.uint8)).sum()), name
+            print("checked", name, flt.n_docs, "numpy", file=sys.stderr, flush=True)
+            rows[name] = dict(terms=terms, op=op, n_docs=flt.n_docs, kernel="xgm_filter_combine_kernel", has_parent=False,
+                              bound_us=round(n_maps * bitmap_bytes / HBM_BYTES_PER_S * 1e6, 3), build=build, parent_plan=None)
+            flt.close()
     db.set_profiling(1)
     db.last_kernel_ms()
     for name, r in rows.items():
@@ -161,6 +199,33 @@ def main():
     db.set_profiling(0)
     for f in (fa, fb):
         f.close()
+    if "all_first" in wanted:
+        # one sample per index: the call that makes the live set (the marking kernel, its count's copy back) and the filter's copy of it
+        samples, source = [], None
+        for i in range(args.first_opens):
+            d2 = open_index()
+            d2.set_profiling(1)
+            d2.last_kernel_ms()
+            t0 = time.perf_counter()
+            flt = d2.filter_all()
+            wall = (time.perf_counter() - t0) * 1e6
+            ms = d2.last_kernel_ms()
+            info = (C.c_uint64 * 4)()
+            _lib.check(_lib.lib().xgm_debug_live_info(d2._h, info))
+            assert info[0] == 1 and info[2] == 1
+            source = {1: "no gaps: rule (a), the lengths are not read", 3: "the lengths: rule (c)"}[info[1]]
+            if i == 0:
+                assert (np.array(flt.words(), dtype=np.uint32) == live).all() and flt.n_docs == d2.get_doccount()
+            samples.append(dict(wall_us=round(wall, 2), kernel_us=round(ms * 1e3, 2) if ms >= 0 else None))
+            flt.close()
+            d2.close()
+        in_bytes = 4 * (last + 1) if info[1] == 3 else 0
+        rows["all_first"] = dict(op="MatchAll, the call that makes the live set", source=source, samples=samples,
+                                 wall_us=statistics.median(x["wall_us"] for x in samples),
+                                 kernel_us=statistics.median(x["kernel_us"] for x in samples) if all(x["kernel_us"] is not None for x in samples) else None,
+                                 bound_us=round((in_bytes + bitmap_bytes + 2 * bitmap_bytes) / HBM_BYTES_PER_S * 1e6, 3), parent_us=None, below_parent=None,
+                                 note="kernel_us: the event pair spans the marking kernel, the host's wait for its count and the copying kernel")
+        print("all_first", rows["all_first"]["kernel_us"], rows["all_first"]["wall_us"], rows["all_first"]["bound_us"], source, file=sys.stderr, flush=True)
     out = {"tool": "tools/filter_query_time.py", "emulated": emulated, "docs": last, "stripes": n_stripes, "calls": args.calls, "warmup": args.warmup,
            "parent_calls": args.parent_calls, "bitmap_bytes": bitmap_bytes,
            "bound": "(1 KB per non-empty (container term, stripe) + 4 B per flat posting + padded bitmap bytes) at 8 TB/s; combine: three bitmaps",

@@ -104,6 +104,7 @@ XGM_MAX_RANGES = 4
 XGM_ORD_MAX = 0xFFFFFFFF
 XGM_RANGE_NO_END = 1
 XGM_FILTER_AND, XGM_FILTER_OR, XGM_FILTER_AND_NOT = 1, 2, 3          # xgm_filter_combine
+XGM_FILTER_NOT, XGM_FILTER_XOR = 4, 5                                # ... live & ~a (b is None); a ^ b
 
 
 class Hit(C.Structure):
@@ -153,6 +154,11 @@ _API = [
     ("xgm_filter_free", None, [C.c_void_p]),
     ("xgm_filter_build_query", C.c_int, [C.c_void_p, _P(Query), _P(C.c_void_p), _P(C.c_uint64)]),
     ("xgm_filter_combine", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, _P(C.c_void_p), _P(C.c_uint64)]),
+    ("xgm_filter_all", C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_uint64)]),
+    ("xgm_index_attach_live", C.c_int, [C.c_void_p, _P(C.c_uint32), C.c_uint32]),
+    ("xgm_index_attach_live_file", C.c_int, [C.c_void_p, C.c_char_p]),
+    ("xgm_glass_export_live", C.c_int, [C.c_char_p, C.c_char_p]),
+    ("xgm_debug_live_info", C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     ("xgm_search_filtered", C.c_int, [C.c_void_p, _P(Query), C.c_void_p, _P(SortSpec), _P(Hit), _P(C.c_uint32), _P(ResultHdr), C.c_int32, _P(C.c_uint32), C.c_uint32]),
     ("xgm_search_filtered_batch", C.c_int, [C.c_void_p, _P(Query), C.c_uint32, C.c_void_p, _P(SortSpec), C.c_uint32, _P(Hit), _P(C.c_uint32), _P(ResultHdr),
                                    C.c_int32, _P(C.c_uint32), C.c_uint32]),

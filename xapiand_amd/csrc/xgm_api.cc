@@ -313,6 +313,7 @@ extern "C" void xgm_index_close(xgm_index* idx) {
     if (idx->d_dense_p2) hipFree(idx->d_dense_p2);
     if (idx->d_dense_wdf0) hipFree(idx->d_dense_wdf0);
     if (idx->d_dense_data) hipFree(idx->d_dense_data);
+    if (idx->d_live) hipFree(idx->d_live);
     for (auto& c : idx->columns) if (c.second.first) hipFree(c.second.first);
     for (auto& c : idx->list_columns) { if (c.second.head) hipFree(c.second.head); if (c.second.ext) hipFree(c.second.ext); }
     for (void* c : idx->retired_columns) hipFree(c);
@@ -2113,7 +2114,7 @@ extern "C" int xgm_column_ord_range(const char* column_path, const char* begin, 
     return XGM_OK;
 }
 
-/* What every producer of a filter does around its kernel — xgm_filter_build, xgm_filter_build_query, xgm_filter_combine: a scratch of the pool, the
+/* What every producer of a filter does around its kernel — xgm_filter_build, xgm_filter_build_query, xgm_filter_combine, xgm_filter_all: a scratch of the pool, the
  * counter, the bitmap, the event pair under xgm_index_set_profiling (tools/filter_time.py, tools/filter_query_time.py), one copy back, the filter.  launch(d_bits, n_padded, d_count, stream) enqueues the kernel. */
 template <class Launch>
 static int filter_produce(xgm_index* idx, const char* kernel_name, Launch&& launch, xgm_filter** out, uint64_t* n_docs) {
@@ -2301,14 +2302,133 @@ extern "C" int xgm_filter_build_query(xgm_index* idx, const xgm_query* plan, xgm
     }, out, n_docs);
 }
 
-extern "C" int xgm_filter_combine(xgm_index* idx, uint32_t op, const xgm_filter* a, const xgm_filter* b, xgm_filter** out, uint64_t* n_docs) {
-    if (!idx || !a || !b || !out) return xgm_set_error(XGM_E_INVALID, "null argument");
+/* ---- the live set; MatchAll and the complement (include/xgm.h: xgm_filter_all, XGM_FILTER_NOT, xgm_index_attach_live) --------------------
+ * "The documents that exist" as one more bitmap in the filter layout, kept by the index.  The first of: (a) no gaps — doccount == lastdocid, every
+ * docid is live whatever its length; (b) an attached set, as attached; (c) doclen[d] != 0 marked and counted by xgm_filter_mark_live_kernel
+ * (xgm_filter_live.h), kept only when the count IS doccount — otherwise some live document has length 0 (all its postings are boolean), the lengths
+ * cannot tell it from a deleted one, and every call that needs the set is declined until a set is attached. */
+
+static void filter_words_of(const xgm_index* idx, uint32_t* n_words, uint32_t* n_padded) {
+    *n_words = (uint32_t)(((uint64_t)idx->hdr.lastdocid + 1u + 31u) / 32u);
+    *n_padded = (uint32_t)(((uint64_t)*n_words + XGM_FILTER_PAD_WORDS - 1u) / XGM_FILTER_PAD_WORDS * XGM_FILTER_PAD_WORDS);
+}
+
+/* *out = the index's live set on the device, made on the first call (the kernel goes to `stream` and is waited for) under live_mu: concurrent first
+ * calls make it once.  XGM_UNSUPPORTED, every time, where rule (c) declines. */
+static int live_set(xgm_index* idx, hipStream_t stream, const uint32_t** out) {
+    std::lock_guard<std::mutex> lk(idx->live_mu);
+    if (idx->live_state == 0) {
+        uint32_t n_words, n_padded;
+        filter_words_of(idx, &n_words, &n_padded);
+        /* (XGM_LIVE_FROM_LENGTHS: a measuring switch — an index without gaps marks its set by rule (c) all the same, tools/filter_query_time.py) */
+        const bool all = idx->hdr.doccount == idx->hdr.lastdocid && !getenv("XGM_LIVE_FROM_LENGTHS");
+        DeviceBuffers tmp;
+        unsigned long long* d_count = nullptr;
+        uint32_t* d_bits = nullptr;
+        int rc = tmp.alloc((void**)&d_count, 8);
+        if (rc) return rc;
+        HIP_TRY(hipMalloc((void**)&d_bits, (size_t)n_padded * 4));
+        unsigned long long count = 0;
+        hipError_t e = hipMemsetAsync(d_count, 0, 8, stream);
+        if (e == hipSuccess) {
+            rc = xgm_launch_filter_mark_live(idx->view.doclen, all, idx->hdr.lastdocid, n_padded, d_bits, d_count, stream);
+            if (rc) { hipStreamSynchronize(stream); hipFree(d_bits); return rc; }
+            ++idx->live_launches;
+            e = hipMemcpyAsync(&count, d_count, 8, hipMemcpyDeviceToHost, stream);
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(stream);
+        if (e != hipSuccess) { hipStreamSynchronize(stream); hipFree(d_bits); return xgm_launch_error("xgm_filter_mark_live_kernel", (int)e, hipGetErrorString(e)); }
+        idx->live_marked = count;
+        if (count == idx->hdr.doccount) { idx->d_live = d_bits; idx->live_source = all ? 1u : 3u; idx->live_state = 1; }
+        else { hipFree(d_bits); idx->live_state = 2; }
+    }
+    if (idx->live_state != 1)
+        return xgm_set_error(XGM_UNSUPPORTED, "live set: %llu documents of non-zero length, doccount %u, lastdocid %u — live documents of length 0 cannot be told from "
+                             "deleted ones: attach the shard's live set (xgm_index_attach_live)", (unsigned long long)idx->live_marked, idx->hdr.doccount, idx->hdr.lastdocid);
+    *out = (const uint32_t*)idx->d_live;
+    return XGM_OK;
+}
+
+extern "C" int xgm_index_attach_live(xgm_index* idx, const uint32_t* words, uint32_t n_words) {
+    if (!idx || !words) return xgm_set_error(XGM_E_INVALID, "null argument");
+    if (idx->device == XGM_DEVICE_NONE) return xgm_set_error(XGM_E_NO_DEVICE, "index opened without a device");
+    uint32_t want_words, n_padded;
+    filter_words_of(idx, &want_words, &n_padded);
+    const uint32_t last = idx->hdr.lastdocid;
+    if (n_words != want_words) return xgm_set_error(XGM_E_INVALID, "live set of %u words, index of %u documents needs %u (another revision?)", n_words, last, want_words);
+    if (words[0] & 1u) return xgm_set_error(XGM_E_INVALID, "live set: bit 0 is set (docid 0 does not exist)");
+    if ((last & 31u) != 31u && (words[n_words - 1u] >> ((last & 31u) + 1u)) != 0u) return xgm_set_error(XGM_E_INVALID, "live set: a bit beyond lastdocid %u is set", last);
+    uint64_t pop = 0;
+    for (uint32_t i = 0; i < n_words; ++i) pop += (uint64_t)__builtin_popcount(words[i]);
+    if (pop != idx->hdr.doccount) return xgm_set_error(XGM_E_INVALID, "live set of %llu documents, index of %u", (unsigned long long)pop, idx->hdr.doccount);
+    int rc = use_device(idx->device);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(idx->live_mu);
+    if (idx->live_state == 1)
+        return xgm_set_error(XGM_E_INVALID, idx->live_source == 2u ? "live set: one is attached already" : "live set: already built (attach before the first use)");
+    std::vector<uint32_t> padded(n_padded, 0u);
+    memcpy(padded.data(), words, (size_t)n_words * 4);
+    void* d = nullptr;
+    HIP_TRY(hipMalloc(&d, (size_t)n_padded * 4));
+    hipError_t e = hipMemcpy(d, padded.data(), (size_t)n_padded * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { hipFree(d); return xgm_launch_error("live set upload", (int)e, hipGetErrorString(e)); }
+    idx->d_live = d; idx->live_source = 2; idx->live_state = 1;          /* (after a decline too: nothing was handed out) */
+    return XGM_OK;
+}
+
+extern "C" int xgm_index_attach_live_file(xgm_index* idx, const char* path) {
+    if (!idx || !path) return xgm_set_error(XGM_E_INVALID, "null argument");
+    if (idx->device == XGM_DEVICE_NONE) return xgm_set_error(XGM_E_NO_DEVICE, "index opened without a device");
+    FILE* f = fopen(path, "rb");
+    if (!f) return xgm_set_error(XGM_E_IO, "cannot open %s: %s", path, strerror(errno));
+    char magic[8];
+    uint32_t h32[4];
+    std::vector<uint32_t> words;
+    bool ok = fread(magic, 1, 8, f) == 8 && fread(h32, 4, 4, f) == 4 && memcmp(magic, "XGMLIV1", 8) == 0;
+    if (ok && (h32[0] != idx->hdr.lastdocid || h32[1] != idx->hdr.doccount)) {
+        fclose(f);
+        return xgm_set_error(XGM_E_INVALID, "%s: live set of %u documents up to %u, index of %u up to %u (another revision?)", path, h32[1], h32[0], idx->hdr.doccount, idx->hdr.lastdocid);
+    }
+    ok = ok && h32[2] == (uint32_t)(((uint64_t)h32[0] + 32u) / 32u) && h32[3] == 0u;
+    if (ok) { words.resize(h32[2]); ok = fread(words.data(), 4, words.size(), f) == words.size(); }
+    fclose(f);
+    if (!ok) return xgm_set_error(XGM_E_INVALID, "%s is not a live-set file", path);
+    return xgm_index_attach_live(idx, words.data(), (uint32_t)words.size());
+}
+
+extern "C" int xgm_debug_live_info(xgm_index* idx, uint64_t* out4) {
+    if (!idx || !out4) return xgm_set_error(XGM_E_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(idx->live_mu);
+    out4[0] = idx->live_state; out4[1] = idx->live_source; out4[2] = idx->live_launches; out4[3] = idx->live_marked;
+    return XGM_OK;
+}
+
+/* MatchAll: a copy of the live set that the filter owns — the combine kernel over (live, live), which also counts it */
+extern "C" int xgm_filter_all(xgm_index* idx, xgm_filter** out, uint64_t* n_docs) {
+    if (!idx || !out) return xgm_set_error(XGM_E_INVALID, "null argument");
     *out = nullptr;
     if (idx->device == XGM_DEVICE_NONE) return xgm_set_error(XGM_E_NO_DEVICE, "index opened without a device");
-    if (op < XGM_FILTER_AND || op > XGM_FILTER_AND_NOT) return xgm_set_error(XGM_E_INVALID, "filter combine: op %u (1 .. 3)", op);
-    if (int frc = filter_usable(idx, a)) return frc;
-    if (int frc = filter_usable(idx, b)) return frc;
     return filter_produce(idx, "xgm_filter_combine_kernel", [&](uint32_t* d_bits, uint32_t n_padded, unsigned long long* d_count, hipStream_t stream) {
+        const uint32_t* live = nullptr;
+        if (int lrc = live_set(idx, stream, &live)) return lrc;
+        return xgm_launch_filter_combine(live, live, XGM_FILTER_AND, n_padded, d_bits, d_count, stream);
+    }, out, n_docs);
+}
+
+extern "C" int xgm_filter_combine(xgm_index* idx, uint32_t op, const xgm_filter* a, const xgm_filter* b, xgm_filter** out, uint64_t* n_docs) {
+    if (!idx || !a || !out) return xgm_set_error(XGM_E_INVALID, "null argument");
+    *out = nullptr;
+    if (idx->device == XGM_DEVICE_NONE) return xgm_set_error(XGM_E_NO_DEVICE, "index opened without a device");
+    if (op < XGM_FILTER_AND || op > XGM_FILTER_XOR) return xgm_set_error(XGM_E_INVALID, "filter combine: op %u (1 .. 5)", op);
+    if (op == XGM_FILTER_NOT ? b != nullptr : b == nullptr) return xgm_set_error(XGM_E_INVALID, op == XGM_FILTER_NOT ? "filter combine: NOT takes one filter (b must be NULL)" : "null argument");
+    if (int frc = filter_usable(idx, a)) return frc;
+    if (b) if (int frc = filter_usable(idx, b)) return frc;
+    return filter_produce(idx, "xgm_filter_combine_kernel", [&](uint32_t* d_bits, uint32_t n_padded, unsigned long long* d_count, hipStream_t stream) {
+        if (op == XGM_FILTER_NOT) {                                      /* live & ~a: the live set is the left side AndNotPostList lacks */
+            const uint32_t* live = nullptr;
+            if (int lrc = live_set(idx, stream, &live)) return lrc;
+            return xgm_launch_filter_combine(live, a->d_bits, op, n_padded, d_bits, d_count, stream);
+        }
         return xgm_launch_filter_combine(a->d_bits, b->d_bits, op, n_padded, d_bits, d_count, stream);
     }, out, n_docs);
 }

@@ -160,15 +160,17 @@ __global__ __launch_bounds__(kFqBlock) void xgm_filter_mark_query_kernel(xgm_seg
 
 constexpr uint32_t kFcBlock = 256;
 
-/* out = a & b, a | b or a & ~b over n4 groups of four words: two 16-byte loads and one store per lane and round.  The inputs hold bit 0 and the
- * bits beyond lastdocid clear, and none of the three operations sets a bit that a does not hold or b does not hold. */
+/* out = a & b, a | b, a & ~b or a ^ b over n4 groups of four words: two 16-byte loads and one store per lane and round.  The inputs hold bit 0 and the
+ * bits beyond lastdocid clear, and none of the operations sets a bit that a does not hold or b does not hold: XOR's result lies inside a | b, and
+ * XGM_FILTER_NOT arrives here as (the live set) & ~b, which lies inside the live set — itself a filter, clean like any other — so a complement never
+ * raises docid 0, a docid beyond lastdocid or a deleted one, and nothing is masked. */
 __global__ __launch_bounds__(kFcBlock) void xgm_filter_combine_kernel(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, uint32_t op, uint32_t n4,
                                                                       uint32_t* __restrict__ out, unsigned long long* __restrict__ count) {
     const uint32_t lane = threadIdx.x & 63u;
     uint32_t mine = 0;
     for (uint32_t i = blockIdx.x * kFcBlock + threadIdx.x; i < n4; i += gridDim.x * kFcBlock) {
         const fq_u4 x = reinterpret_cast<const fq_u4*>(a)[i], y = reinterpret_cast<const fq_u4*>(b)[i];
-        const fq_u4 r = op == XGM_FILTER_AND ? x & y : op == XGM_FILTER_OR ? x | y : x & ~y;
+        const fq_u4 r = op == XGM_FILTER_AND ? x & y : op == XGM_FILTER_OR ? x | y : op == XGM_FILTER_XOR ? x ^ y : x & ~y;
         reinterpret_cast<fq_u4*>(out)[i] = r;
         mine += (uint32_t)(__popc(r.x) + __popc(r.y) + __popc(r.z) + __popc(r.w));
     }
@@ -205,7 +207,7 @@ int xgm_launch_filter_mark_query(const xgm_seg_dev& seg, const xgm_filter_progra
 
 int xgm_launch_filter_combine(const uint32_t* a, const uint32_t* b, uint32_t op, uint32_t n_words_padded, uint32_t* out, unsigned long long* count,
                               hipStream_t stream) {
-    if (!a || !b || !out || !count || n_words_padded == 0 || n_words_padded % XGM_FILTER_PAD_WORDS != 0 || op < XGM_FILTER_AND || op > XGM_FILTER_AND_NOT)
+    if (!a || !b || !out || !count || n_words_padded == 0 || n_words_padded % XGM_FILTER_PAD_WORDS != 0 || op < XGM_FILTER_AND || op > XGM_FILTER_XOR)
         return xgm_launch_error("filter combine kernel", 0, "bad arguments");
     const uint32_t n4 = n_words_padded / 4u, n_blocks = (n4 + kFcBlock - 1u) / kFcBlock;
     dim3 grid(n_blocks < 2048u ? n_blocks : 2048u), block(kFcBlock);

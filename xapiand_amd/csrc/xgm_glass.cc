@@ -935,7 +935,59 @@ extern "C" int xgm_glass_export_list_column(const char* glass_dir, uint32_t slot
     return XGM_OK;
 }
 
-extern "C" int xgm_glass_info(const char* glass_dir, uint64_t* revision, uint32_t* doccount, uint32_t* lastdocid, uint64_t* total_length) {
+/* ---- the live set (include/xgm.h: xgm_glass_export_live): which docids the shard holds ------------------------------------------------
+ * A docid is live iff it appears in the doclen list — the postlist the reference's matcher opens for an empty term (Query::MatchAll) — whatever
+ * its length: a document of boolean terms alone is there with length 0, which the segment's doclen[] cannot tell from a deleted one.  Only the
+ * doclen chunks are decoded (read_glass's branch for "\0\xe0" keys); no posting is touched.
+ *   "XGMLIV1\0", u32 lastdocid, u32 doccount, u32 n_words = ceil((lastdocid + 1) / 32), u32 0,
+ *   u32 words[n_words]            bit d & 31 of word d >> 5 set when docid d is live: the filter layout without its padding */
+extern "C" int xgm_glass_export_live(const char* glass_dir, const char* out_path) {
+    if (!glass_dir || !out_path) return xgm_set_error(XGM_E_INVALID, "null argument");
+    const std::string dir(glass_dir);
+    GlassVersion ver;
+    int rc = read_version(dir, &ver);
+    if (rc) return rc;
+    if (ver.last_docid > 0xFFFFFFFEull) return xgm_set_error(XGM_E_INVALID, "docids beyond 32 bits");
+    std::vector<uint32_t> words((size_t)((ver.last_docid + 32u) / 32u), 0u);
+    uint64_t n_live = 0;
+    bool beyond = false, twice = false;
+    Table post;
+    if ((rc = post.open(dir + "/postlist.glass", ver.root[kTablePostlist]))) return rc;
+    rc = post.walk([&](const std::string& key, const std::string& tag) -> int {
+        if (key.size() < 2 || key[0] != '\0' || (uint8_t)key[1] != 0xE0) return XGM_OK;
+        const uint8_t* p = (const uint8_t*)tag.data();
+        const uint8_t* end = p + tag.size();
+        uint64_t first;
+        if (key.size() == 2) {
+            uint64_t n, cf;
+            if (!get_varint(&p, end, &n) || !get_varint(&p, end, &cf) || !get_varint(&p, end, &first)) return xgm_set_error(XGM_E_INVALID, "doclen list: truncated");
+            ++first;
+        } else {
+            const uint8_t* kp = (const uint8_t*)key.data() + 2;
+            if (!get_sortable_uint(&kp, (const uint8_t*)key.data() + key.size(), &first)) return xgm_set_error(XGM_E_INVALID, "doclen list: bad chunk key");
+        }
+        return read_chunk_body(p, end, first, [&](uint64_t d, uint64_t) {
+            if (d == 0 || d > ver.last_docid) { beyond = true; return; }
+            uint32_t& w = words[(size_t)(d >> 5)];
+            const uint32_t bit = 1u << (d & 31u);
+            twice = twice || (w & bit) != 0u;
+            w |= bit;
+            ++n_live;
+        });
+    });
+    if (rc) return rc;
+    if (beyond || twice) return xgm_set_error(XGM_E_INVALID, "doclen list: a docid %s", beyond ? "outside 1 .. the last one" : "listed twice");
+    if (n_live != ver.doccount)
+        return xgm_set_error(XGM_E_INVALID, "doclen list holds %llu documents, the version file says %llu", (unsigned long long)n_live, (unsigned long long)ver.doccount);
+    FILE* f = fopen(out_path, "wb");
+    if (!f) return xgm_set_error(XGM_E_IO, "cannot create %s: %s", out_path, strerror(errno));
+    const uint32_t h32[4] = {(uint32_t)ver.last_docid, (uint32_t)ver.doccount, (uint32_t)words.size(), 0u};
+    const bool ok = fwrite("XGMLIV1", 1, 8, f) == 8 && fwrite(h32, 4, 4, f) == 4 && fwrite(words.data(), 4, words.size(), f) == words.size();
+    if (fclose(f) != 0 || !ok) return xgm_set_error(XGM_E_IO, "short write on %s", out_path);
+    return XGM_OK;
+}
+
+extern "C" int xgm_glass_info(const char* glass_dir,uint64_t* revision, uint32_t* doccount, uint32_t* lastdocid, uint64_t* total_length) {
     if (!glass_dir) return xgm_set_error(XGM_E_INVALID, "null argument");
     GlassVersion v;
     int rc = read_version(glass_dir, &v);

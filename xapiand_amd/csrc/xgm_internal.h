@@ -132,6 +132,14 @@ struct xgm_index {
     struct ListColumn { void* head = nullptr; void* ext = nullptr; uint32_t n_distinct = 0; };
     std::map<uint32_t, ListColumn> list_columns;               /* value slot → (device u32 head[lastdocid + 1], u32 ext[] or null): xgm_index_attach_list_column;
                                                                 * beside `columns`, under columns_mu, replaced arrays to retired_columns */
+    /* the live set (xgm_filter_all, XGM_FILTER_NOT; xgm_api.cc: live_set): made on first use or attached, then never written again.  Under live_mu:
+     * concurrent first calls build it once and all read the same bits */
+    std::mutex live_mu;
+    void* d_live = nullptr;            /* device u32 [n_words padded to XGM_FILTER_PAD_WORDS] in the filter layout, while live_state == 1 */
+    uint32_t live_state = 0;           /* 0 not asked for yet, 1 in d_live, 2 declined: live documents of length 0 and nothing attached */
+    uint32_t live_source = 0;          /* 1 no gaps (doccount == lastdocid), 2 attached (xgm_index_attach_live*), 3 derived from the lengths */
+    uint32_t live_launches = 0;        /* xgm_filter_mark_live_kernel launches so far: at most one (xgm_debug_live_info) */
+    uint64_t live_marked = 0;          /* the kernel's count: documents of non-zero length (source 3, and a declined 2) */
 };
 
 int xgm_lookup_term_id(const xgm_index* idx, const char* term, size_t len, uint32_t* id);

@@ -38,6 +38,7 @@
 #include "xgm_wave.h"
 #include "xgm_posfilter.h"
 #include "xgm_filter.h"
+#include "xgm_filter_live.h"
 #include "xgm_filter_terms.h"
 
 namespace {

@@ -91,7 +91,13 @@ struct xgm_filter_program {
 };
 int xgm_launch_filter_mark_query(const xgm_seg_dev& seg, const xgm_filter_program& pg, uint32_t n_words_padded, uint32_t* bits, unsigned long long* count,
                                  hipStream_t stream);
-/* out = a & b (XGM_FILTER_AND), a | b (_OR) or a & ~b (_AND_NOT) over two such bitmaps of n_words_padded words; *count (zeroed by the caller) += set bits */
+/* the live set (xgm_filter_live.h): the same bitmap, the same padding and the same count for doclen[d] != 0 over the u32 doclen section
+ * [lastdocid + 1] — the caller compares *count with the header's doccount and keeps the bits only when they agree — or, with all set, for every
+ * docid 1 .. lastdocid (doclen is then not read and may be NULL) */
+int xgm_launch_filter_mark_live(const uint32_t* doclen, bool all, uint32_t lastdocid, uint32_t n_words_padded, uint32_t* bits, unsigned long long* count,
+                                hipStream_t stream);
+/* out = a & b (XGM_FILTER_AND), a | b (_OR), a & ~b (_AND_NOT, and XGM_FILTER_NOT with the index's live set as a and the operand as b) or a ^ b (_XOR)
+ * over two such bitmaps of n_words_padded words; *count (zeroed by the caller) += set bits */
 int xgm_launch_filter_combine(const uint32_t* a, const uint32_t* b, uint32_t op, uint32_t n_words_padded, uint32_t* out, unsigned long long* count,
                               hipStream_t stream);
 /* a filter's bitmap as the whole query (xgm_range.h, xgm_search_range): the first k passing documents by docid (ord NULL) or by (value, docid)

@@ -269,6 +269,24 @@ class Database:
         _lib.check(_lib.lib().xgm_filter_build_query(self._h, C.byref(planned), C.byref(h), C.byref(nd)))
         return Filter(h, nd.value, (self._info.lastdocid + 32) // 32, self)
 
+    def filter_all(self):
+        """xgm_filter_all: Query::MatchAll as a filter — the index's live set, one bit per docid that exists → Filter (n_docs == doccount).
+        Unsupported when the shard has deletions AND live documents of length 0 and no live set is attached (attach_live)."""
+        h, nd = C.c_void_p(), C.c_uint64()
+        _lib.check(_lib.lib().xgm_filter_all(self._h, C.byref(h), C.byref(nd)))
+        return Filter(h, nd.value, (self._info.lastdocid + 32) // 32, self)
+
+    def attach_live(self, words):
+        """xgm_index_attach_live: the shard's live set from memory — (lastdocid + 32) // 32 words, bit d & 31 of word d >> 5 set when docid d
+        exists — before the first filter_all / filter_not."""
+        import numpy as np
+        w = np.ascontiguousarray(words, dtype=np.uint32)
+        _lib.check(_lib.lib().xgm_index_attach_live(self._h, w.ctypes.data_as(C.POINTER(C.c_uint32)), len(w)))
+
+    def attach_live_file(self, path):
+        """xgm_index_attach_live_file: the same from a file of xgm_glass_export_live."""
+        _lib.check(_lib.lib().xgm_index_attach_live_file(self._h, _as_bytes(path)))
+
     def set_stream(self, hip_stream):
         _lib.check(_lib.lib().xgm_index_set_stream(self._h, C.c_void_p(hip_stream)))
 
@@ -295,11 +313,12 @@ class Filter:
         self._h, self.n_docs, self._n_words, self._db = handle, n_docs, n_words, db
 
     def combine(self, other, op, db=None):
-        """xgm_filter_combine: self & other (_lib.XGM_FILTER_AND), self | other (_OR) or self & ~other (_AND_NOT) as a new Filter; both stay as
-        they are.  db: the Database the filters belong to (a filter remembers the one that built it)."""
-        db = db or self._db or other._db
+        """xgm_filter_combine: self & other (_lib.XGM_FILTER_AND), self | other (_OR), self & ~other (_AND_NOT) or self ^ other (_XOR) as a new
+        Filter, or — other None, _lib.XGM_FILTER_NOT — the live documents outside self; the inputs stay as they are.  db: the Database the filters
+        belong to (a filter remembers the one that built it)."""
+        db = db or self._db or (other._db if other is not None else None)
         h, nd = C.c_void_p(), C.c_uint64()
-        _lib.check(_lib.lib().xgm_filter_combine(db._h, op, self._h, other._h, C.byref(h), C.byref(nd)))
+        _lib.check(_lib.lib().xgm_filter_combine(db._h, op, self._h, other._h if other is not None else None, C.byref(h), C.byref(nd)))
         return Filter(h, nd.value, self._n_words, db)
 
     def words(self):
@@ -564,6 +583,21 @@ def filter_or(db, a, b):
 def filter_and_not(db, a, b):
     """a & ~b"""
     return a.combine(b, _lib.XGM_FILTER_AND_NOT, db)
+
+
+def filter_all(db):
+    """Query::MatchAll as a filter: the documents that exist (xgm_filter_all)."""
+    return db.filter_all()
+
+
+def filter_not(db, f):
+    """live & ~f, the DSL's bare `_not` (xgm_filter_combine, XGM_FILTER_NOT)."""
+    return f.combine(None, _lib.XGM_FILTER_NOT, db)
+
+
+def filter_xor(db, a, b):
+    """a ^ b (xgm_filter_combine)."""
+    return a.combine(b, _lib.XGM_FILTER_XOR, db)
 
 
 def search_filtered(db, planned, flt, sort_by=None, slot=0, reverse=False, spy=None):
