@@ -604,12 +604,37 @@ void xgm_filter_free(xgm_filter*);
  * XGM_E_INVALID: a null idx / plan / out, a plan that is not well formed (a term id beyond the dictionary, masks or tree operands out of
  * range); XGM_E_NO_DEVICE: an index without a device; XGM_UNSUPPORTED: an ACTIVE positional plan (PHRASE / NEAR with phrase_active), a tree
  * that reuses a node so often that its expansion exceeds the kernel's program.
- * NOT offered: positional plans; several plans in one launch; shards; xgm_mset_bounds* of a search under such a filter.  (Which documents EXIST
+ * NOT offered: positional plans; shards; xgm_mset_bounds* of a search under such a filter.  (Several plans in one launch:
+ * xgm_filter_build_query_batch below.)  (Which documents EXIST
  * is another producer's question: xgm_filter_all, and XGM_FILTER_NOT of xgm_filter_combine for a complement.)  The matcher hook does not lower to
  * this call yet.
  * Replaces: OP_FILTER's boolean right-hand side and Query(OP_SCALE_WEIGHT, q, 0) as the matcher walks them per candidate
  * (matcher/matcher.cc:482-536); for `_range`, the accuracy-term side of OP_FILTER(MultipleValue*, terms). */
 int xgm_filter_build_query(xgm_index*, const xgm_query* plan, xgm_filter** out, uint64_t* n_docs /* may be NULL */);
+
+/* The same for n_plans (1 .. XGM_FILTER_BATCH_MAX) plans at once, all under one base filter — what a dashboard sends: ten facet values each under
+ * "last 30 days AND text matches", a `_filter` aggregation per bucket.  ONE launch, one allocation, one copy back and one synchronisation whatever
+ * n_plans is, where n single calls and n combines pay each of them n or 2n times.
+ * out[i] holds, word for word, what xgm_filter_combine(XGM_FILTER_AND, xgm_filter_build_query(plans[i]), under) holds — with under == NULL, what
+ * xgm_filter_build_query(plans[i]) holds — and n_docs[i] (n_docs may be NULL) its count.  Each out[i] is an ordinary xgm_filter with
+ * xgm_filter_build's contract (padded, every padded word written, bit 0 and the bits beyond lastdocid clear, immutable, bound to the index's
+ * lastdocid), taken by every consumer of a filter and freed by xgm_filter_free on its own.  Duplicate plans are allowed and give equal bitmaps.
+ * `under` is only read; a unit of 8192 documents none of which passes it costs a load of `under` and a store of zeros, nothing of the plan's
+ * terms.
+ * MEMORY: the n_plans bitmaps live in ONE device allocation that the batch's filters share.  xgm_filter_free may be called on them in any order
+ * and from any thread; the batch's memory is returned when the LAST of its filters is freed — a long-lived filter of a batch keeps the whole
+ * batch's n_plans * ceil((lastdocid + 1) / 2048) * 256 bytes.  (A filter made by any other call owns its bitmap alone, as before.)
+ * ALL OR NOTHING: the plans are compiled in order before anything is allocated or launched.  The first plan that is not accepted decides the
+ * return value — XGM_UNSUPPORTED or XGM_E_INVALID exactly as xgm_filter_build_query decides for that plan alone; the text of xgm_last_error names
+ * its index — and on this and on every later failure (XGM_E_NOMEM: the device allocation; XGM_E_DEVICE) every out[i] is NULL and nothing is
+ * kept.  XGM_E_INVALID also for a null idx / plans / out, n_plans == 0 or above XGM_FILTER_BATCH_MAX (out is then not touched) and an `under`
+ * of another device or lastdocid; XGM_E_NO_DEVICE: an index without a device.  Synchronous; safe from any number of threads on one index.
+ * NOT offered: positional plans; a different base filter per plan; a base filter combined by anything but AND; shards. */
+#define XGM_FILTER_BATCH_MAX 64u
+int xgm_filter_build_query_batch(xgm_index*, const xgm_query* plans, uint32_t n_plans, const xgm_filter* under /* may be NULL */,
+                                 xgm_filter** out /* [n_plans] */, uint64_t* n_docs /* [n_plans], may be NULL */);
+/* (tests) the calling thread's last successful batch: kernel launches, (plan, unit) work items, waves launched, work items skipped under `under` */
+int xgm_debug_filter_batch_info(uint64_t* out4);
 
 /* A new filter from two filters of the same index and lastdocid: a & b, a | b, a & ~b or a ^ b, word by word on the device; a and b stay as they
  * are (a == b is allowed), *n_docs (may be NULL) = the documents of the result.  DSL `_and` / `_or` / `_not` / `_xor` BETWEEN restrictions: two
@@ -620,7 +645,7 @@ int xgm_filter_build_query(xgm_index*, const xgm_query* plan, xgm_filter** out, 
  * XGM_E_INVALID: a null idx / a / out, a null b for any op but NOT, a non-null b for NOT, an op outside 1 .. 5, a filter of another device or
  * lastdocid; XGM_E_NO_DEVICE: an index without a device; XGM_UNSUPPORTED (XGM_FILTER_NOT only): the index cannot tell its live documents from its
  * deleted ones and no live set is attached — see xgm_filter_all; the text of xgm_last_error names xgm_index_attach_live.
- * NOT offered: more than two operands in one call; positional plans as operands, several plans per launch, shards and xgm_mset_bounds* (the filters'
+ * NOT offered: more than two operands in one call; positional plans as operands, several combines per launch, shards and xgm_mset_bounds* (the filters'
  * own limits); MatchAll or a complement as a WEIGHTED subquery inside an AND / OR tree of xgm_plan_query — these are filters, they weigh nothing.
  * Replaces: MultiAndPostList / OrPostList / AndNotPostList (and OP_XOR's postlist) over unweighted sub-trees under OP_FILTER
  * (matcher/matcher.cc:482-536); for XGM_FILTER_NOT, AndNotPostList (matcher/andnotpostlist.cc) whose left side is the doclen-list postlist the matcher

@@ -10,6 +10,11 @@
   all_first                         the ONE xgm_filter_all that makes the live set, on a freshly built (or opened) index: one sample per index,
                                     --first-opens of them, every sample listed; XGM_LIVE_FROM_LENGTHS=1 makes an index without gaps — the synthetic one —
                                     mark its set from the lengths (rule (c): the doclen section in, the bitmap out) instead of by rule (a) (the bitmap out)
+  batch10                           ONE xgm_filter_build_query_batch call over ten plans (term_r1, term_r100, term_r10000, and3, or5 and five more of
+                                    the same kinds): wall_us / kernel_us of the one call, beside singles_wall_us / singles_kernel_us — the same ten
+                                    filters by ten xgm_filter_build_query calls, timed as one sequence (the kernel times summed)
+  batch10_under                     the same ten plans under term_r100's filter; the single route is then ten builds and ten xgm_filter_combine(AND)
+                                    Against a library from before the batch call (XGM_LIB_PATH) both rows hold the single route alone.
 --rows a,b,... measures only those rows (an A/B of one row between two builds of the library).
 Per row: the median over --calls calls (after --warmup) of
   kernel_us   the hipEvent pair the call records around its kernel (xgm_index_set_profiling / xgm_last_kernel_ms, read after each call)
@@ -44,6 +49,9 @@ CORPUS_SEED = 0x5EED0001
 HBM_BYTES_PER_S = 8e12
 ROWS = [("term_r1", "OR", ["t1"]), ("term_r100", "OR", ["t100"]), ("term_r10000", "OR", ["t10000"]), ("and3", "AND", ["t3", "t7", "t15"]),
         ("or5", "OR", ["t9", "t40", "t300", "t2000", "t7"]), ("or16", "OR", ["t%d" % (200 + 37 * i) for i in range(16)])]
+# batch10: the first five rows above and five more of the same kinds — a dashboard's ten restrictions, some of whose terms recur
+BATCH_ROWS = ROWS[:5] + [("term_r10", "OR", ["t10"]), ("term_r1000", "OR", ["t1000"]), ("term_r50", "OR", ["t50"]), ("and3b", "AND", ["t3", "t11", "t40"]),
+                         ("or5b", "OR", ["t12", "t40", "t400", "t3000", "t7"])]
 
 
 def make_plan(db, op, terms):
@@ -123,7 +131,7 @@ def main():
     def open_index():
         return Database(args.segment) if args.segment else Database.synthetic(CORPUS_SEED, args.docs, args.vocab, with_positions=False)
     db = open_index()
-    names = [n for n, _, _ in ROWS] + ["combine", "not", "xor", "all", "all_first"]
+    names = [n for n, _, _ in ROWS] + ["combine", "not", "xor", "all", "batch10", "batch10_under", "all_first"]
     wanted = set(args.rows.split(",")) if args.rows else set(names)
     assert wanted <= set(names), sorted(wanted - set(names))
     last = db.get_lastdocid()
@@ -196,6 +204,73 @@ def main():
         db.set_profiling(1)
         r["below_parent"] = None if r["parent_us"] is None else r["wall_us"] < r["parent_us"]
         print(name, r["kernel_us"], r["wall_us"], r["bound_us"], r["parent_us"], file=sys.stderr, flush=True)
+    # ten plans at once: ONE xgm_filter_build_query_batch call beside the same ten filters by ten single calls (+ ten combines)
+    for name in ("batch10", "batch10_under"):
+        if name not in wanted:
+            continue
+        plans10 = [make_plan(db, op, terms) for _, op, terms in BATCH_ROWS]
+        under = fb if name == "batch10_under" else None
+
+        def singles():
+            """The single-call route: (the ten filters, the sum of the calls' kernel times in µs or None)."""
+            out, kern = [], 0.0
+            for p in plans10:
+                f = db.build_query_filter(p)
+                ms = [db.last_kernel_ms()]
+                if under is not None:
+                    one, f = f, f.combine(under, _lib.XGM_FILTER_AND)
+                    ms.append(db.last_kernel_ms())
+                    one.close()
+                out.append(f)
+                kern = None if kern is None or min(ms) < 0 else kern + sum(ms) * 1e3
+            return out, kern
+
+        def batch():
+            out = db.build_query_filters(plans10, under)
+            ms = db.last_kernel_ms()
+            return out, (ms * 1e3 if ms >= 0 else None)
+        has_batch = hasattr(db, "build_query_filters")                           # (an A/B against a library from before the call: the single route alone)
+        ref, _ = singles()
+        r = dict(plans=[n for n, _, _ in BATCH_ROWS], under="term_r100" if under is not None else None, n_docs=[f.n_docs for f in ref],
+                 kernel="xgm_filter_mark_query_batch_kernel", launches_single=len(ref) * (2 if under is not None else 1))
+        if has_batch:
+            got, _ = batch()
+            for g, f in zip(got, ref):
+                assert g.words() == f.words() and g.n_docs == f.n_docs, name
+            info = (C.c_uint64 * 4)()
+            _lib.lib().xgm_debug_filter_batch_info(info)
+            r.update(launches=int(info[0]), work_items=int(info[1]), waves=int(info[2]), skipped_items=int(info[3]))
+            for g in got:
+                g.close()
+            print("checked", name, r["n_docs"], "the single-call route", file=sys.stderr, flush=True)
+        for f in ref:
+            f.close()
+        db.set_profiling(1)
+        db.last_kernel_ms()
+        for key, fn in (("batch", batch if has_batch else None), ("singles", singles)):
+            if fn is None:
+                r["wall_us"] = r["kernel_us"] = None
+                continue
+            got = []
+            for i in range(args.warmup + args.calls):
+                t0 = time.perf_counter()
+                fs, kern = fn()
+                dt = (time.perf_counter() - t0) * 1e6
+                for f in fs:
+                    f.close()
+                if i >= args.warmup:
+                    got.append((dt, kern))
+            kerns = [k for _, k in got if k is not None]
+            wall, kern = round(statistics.median(dt for dt, _ in got), 2), (round(statistics.median(kerns), 2) if kerns else None)
+            if key == "batch":
+                assert db.last_kernel_name() == r["kernel"], (name, db.last_kernel_name())
+                r["wall_us"], r["kernel_us"] = wall, kern
+            else:
+                r["singles_wall_us"], r["singles_kernel_us"] = wall, kern
+        db.set_profiling(0)
+        r["wall_ratio"] = round(r["singles_wall_us"] / r["wall_us"], 2) if r["wall_us"] else None
+        rows[name] = dict(r, bound_us=None, parent_us=None, below_parent=None)
+        print(name, r["kernel_us"], r["wall_us"], "singles", r["singles_kernel_us"], r["singles_wall_us"], file=sys.stderr, flush=True)
     db.set_profiling(0)
     for f in (fa, fb):
         f.close()

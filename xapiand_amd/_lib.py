@@ -105,6 +105,7 @@ XGM_ORD_MAX = 0xFFFFFFFF
 XGM_RANGE_NO_END = 1
 XGM_FILTER_AND, XGM_FILTER_OR, XGM_FILTER_AND_NOT = 1, 2, 3          # xgm_filter_combine
 XGM_FILTER_NOT, XGM_FILTER_XOR = 4, 5                                # ... live & ~a (b is None); a ^ b
+XGM_FILTER_BATCH_MAX = 64                                            # xgm_filter_build_query_batch
 
 
 class Hit(C.Structure):
@@ -153,6 +154,8 @@ _API = [
     ("xgm_filter_read", C.c_int, [C.c_void_p, _P(C.c_uint32), C.c_uint32]),
     ("xgm_filter_free", None, [C.c_void_p]),
     ("xgm_filter_build_query", C.c_int, [C.c_void_p, _P(Query), _P(C.c_void_p), _P(C.c_uint64)]),
+    ("xgm_filter_build_query_batch", C.c_int, [C.c_void_p, _P(Query), C.c_uint32, C.c_void_p, _P(C.c_void_p), _P(C.c_uint64)]),
+    ("xgm_debug_filter_batch_info", C.c_int, [_P(C.c_uint64)]),
     ("xgm_filter_combine", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, _P(C.c_void_p), _P(C.c_uint64)]),
     ("xgm_filter_all", C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_uint64)]),
     ("xgm_index_attach_live", C.c_int, [C.c_void_p, _P(C.c_uint32), C.c_uint32]),

@@ -15,6 +15,7 @@
 #include <cstring>
 #include <string>
 
+#include "xgm_filter_hold.h"
 #include "xgm_internal.h"
 #include "xgm_launch.h"
 
@@ -80,6 +81,7 @@ struct XgmScratch {
     bool inorder = false;                                       /* this batch's upload and download go on the batch's stream (the dispatcher's small batches: fewer HIP calls) */
     bool arrive_dirty = false;                                  /* a fused launch on this scratch was not enqueued completely: zero the counters before the next */
     uint32_t* d_arrive = nullptr; size_t cap_arrive = 0;        /* per-query arrival counters of a launch that finishes its queries itself (zero between launches) */
+    unsigned char* d_fbatch = nullptr;                          /* xgm_filter_build_query_batch: kFilterBatchBytes — the counters first, the programs at its END */
     /* pinned host */
     void* h_up = nullptr; size_t cap_up = 0;
     void* h_down = nullptr; size_t cap_down = 0;
@@ -176,6 +178,7 @@ static void scratch_destroy(XgmScratch* s) {
     hipFree(s->d_cand); hipFree(s->d_ghdr); hipFree(s->d_in); hipFree(s->d_mkq); hipFree(s->d_hist);
     hipFree(s->d_arena); hipFree(s->d_count);
     hipFree(s->d_hits); hipFree(s->d_hdrs); hipFree(s->d_part_hits); hipFree(s->d_part_hdrs); hipFree(s->d_arrive); hipFree(s->d_sorted); hipFree(s->d_all);
+    hipFree(s->d_fbatch);
     if (s->h_sorted) hipHostFree(s->h_sorted);
     if (s->h_up) hipHostFree(s->h_up);
     if (s->h_down) hipHostFree(s->h_down);
@@ -1763,6 +1766,7 @@ struct xgm_filter {
     uint32_t n_words = 0, n_words_padded = 0;    /* ceil((lastdocid + 1) / 32); that rounded up to XGM_FILTER_PAD_WORDS */
     uint32_t* d_bits = nullptr;
     uint64_t n_docs = 0;
+    FilterBatchHold* hold = nullptr;             /* a filter of xgm_filter_build_query_batch: d_bits lies inside hold->d_mem, which the batch's filters share (xgm_filter_hold.h) */
 };
 
 static int filter_usable(const xgm_index* idx, const xgm_filter* flt) {
@@ -2199,7 +2203,12 @@ extern "C" int xgm_filter_read(const xgm_filter* flt, uint32_t* words, uint32_t 
 
 extern "C" void xgm_filter_free(xgm_filter* flt) {
     if (!flt) return;
-    if (use_device(flt->device) == XGM_OK) hipFree(flt->d_bits);
+    if (FilterBatchHold* h = flt->hold) {        /* one of a batch: its memory goes with the LAST of the batch's filters */
+        if (h->drop()) {
+            if (use_device(flt->device) == XGM_OK) hipFree(h->d_mem);
+            delete h;
+        }
+    } else if (use_device(flt->device) == XGM_OK) hipFree(flt->d_bits);
     delete flt;
 }
 
@@ -2300,6 +2309,83 @@ extern "C" int xgm_filter_build_query(xgm_index* idx, const xgm_query* plan, xgm
     return filter_produce(idx, "xgm_filter_mark_query_kernel", [&](uint32_t* d_bits, uint32_t n_padded, unsigned long long* d_count, hipStream_t stream) {
         return xgm_launch_filter_mark_query(idx->view, pg, n_padded, d_bits, d_count, stream);
     }, out, n_docs);
+}
+
+/* ---- several plans in one launch, under a base filter (include/xgm.h: xgm_filter_build_query_batch) ----------------------------------------
+ * filter_produce's frame for n bitmaps: one scratch, one memset of the counters, one upload of the programs, one launch, one copy back, one
+ * synchronisation — and ONE allocation, shared by the n filters through a FilterBatchHold.  The scratch keeps kFilterBatchBytes of device memory
+ * for the call: the counters (one per plan and one for the skipped work items) at its start, the programs at its END — the array's last entry
+ * ends where the allocation ends. */
+static_assert(XGM_FILTER_BATCH_MAX == XGM_FQ_BATCH_MAX, "include/xgm.h and xgm_launch.h agree on the batch's size");
+constexpr size_t kFilterBatchCounters = ((size_t)XGM_FILTER_BATCH_MAX + 1u) * XGM_FQ_COUNT_STRIDE * 8u + 128u;   /* a counter per 128-byte line, rounded to 256 bytes */
+constexpr size_t kFilterBatchBytes = kFilterBatchCounters + (size_t)XGM_FILTER_BATCH_MAX * sizeof(xgm_filter_program);
+static_assert(kFilterBatchCounters % 256 == 0 && sizeof(xgm_filter_program) % 8 == 0, "the scratch's layout");
+static thread_local uint64_t t_filter_batch_info[4];
+extern "C" int xgm_debug_filter_batch_info(uint64_t* out4) { if (!out4) return -1; memcpy(out4, t_filter_batch_info, sizeof t_filter_batch_info); return 0; }
+
+extern "C" int xgm_filter_build_query_batch(xgm_index* idx, const xgm_query* plans, uint32_t n_plans, const xgm_filter* under, xgm_filter** out, uint64_t* n_docs) {
+    if (!idx || !plans || !out) return xgm_set_error(XGM_E_INVALID, "null argument");
+    if (n_plans == 0 || n_plans > XGM_FILTER_BATCH_MAX) return xgm_set_error(XGM_E_INVALID, "query filter batch: %u plans (1 .. %u)", n_plans, XGM_FILTER_BATCH_MAX);
+    for (uint32_t i = 0; i < n_plans; ++i) out[i] = nullptr;
+    if (idx->device == XGM_DEVICE_NONE) return xgm_set_error(XGM_E_NO_DEVICE, "index opened without a device");
+    if (under) if (int frc = filter_usable(idx, under)) return frc;
+    /* every plan compiled, in order, before anything is allocated or launched: the first that is declined decides the call */
+    std::vector<xgm_filter_program> pgs(n_plans);
+    for (uint32_t i = 0; i < n_plans; ++i) {
+        const int prc = filter_program_of(idx, &plans[i], &pgs[i]);
+        if (prc == XGM_UNSUPPORTED) return xgm_set_error(XGM_UNSUPPORTED, "query filter batch: plan %u is not supported (an active positional plan, or a tree beyond the kernel's program)", i);
+        if (prc) { const std::string why = xgm_last_error(); return xgm_set_error(prc, "query filter batch: plan %u: %s", i, why.c_str()); }
+    }
+    int rc = use_device(idx->device);
+    if (rc) return rc;
+    const uint32_t n_words = (uint32_t)(((uint64_t)idx->hdr.lastdocid + 1u + 31u) / 32u);
+    const uint32_t n_padded = (uint32_t)(((uint64_t)n_words + XGM_FILTER_PAD_WORDS - 1u) / XGM_FILTER_PAD_WORDS * XGM_FILTER_PAD_WORDS);
+    XgmScratch* sc;
+    if ((rc = scratch_acquire(idx, &sc))) return rc;
+    ScratchRelease release_{idx, sc};
+    if (!sc->d_fbatch) HIP_TRY(hipMalloc((void**)&sc->d_fbatch, kFilterBatchBytes));
+    if ((rc = grow_pinned(&sc->h_sorted, &sc->cap_hsorted, kFilterBatchBytes))) return rc;
+    const size_t pg_bytes = (size_t)n_plans * sizeof(xgm_filter_program), o_pgs = kFilterBatchBytes - pg_bytes,
+                 count_bytes = ((size_t)n_plans + 1u) * XGM_FQ_COUNT_STRIDE * 8u;
+    unsigned char* hb = (unsigned char*)sc->h_sorted;
+    unsigned long long* d_count = (unsigned long long*)sc->d_fbatch;
+    const xgm_filter_program* d_pgs = (const xgm_filter_program*)(sc->d_fbatch + o_pgs);
+    const unsigned long long* h_count = (const unsigned long long*)hb;
+    memcpy(hb + o_pgs, pgs.data(), pg_bytes);
+    /* the n bitmaps: bitmap i at i * n_padded words, a multiple of 256 bytes */
+    void* d_mem = nullptr;
+    hipError_t e = hipMalloc(&d_mem, (size_t)n_plans * n_padded * 4);
+    if ((int)e == 2 /* hipErrorOutOfMemory */) { (void)hipGetLastError(); return xgm_set_error(XGM_E_NOMEM, "query filter batch: out of device memory (%zu bytes)", (size_t)n_plans * n_padded * 4); }
+    if (e != hipSuccess) return xgm_launch_error("hipMalloc", (int)e, hipGetErrorString(e));
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;                             /* xgm_index_set_profiling: a pair around the kernel (tools/filter_query_time.py) */
+    if ((rc = next_event_pair(idx, &ev0, &ev1))) { hipFree(d_mem); return rc; }
+    uint32_t n_items = 0, grid = 0;
+    e = hipMemsetAsync(d_count, 0, count_bytes, sc->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(sc->d_fbatch + o_pgs, hb + o_pgs, pg_bytes, hipMemcpyHostToDevice, sc->stream);
+    if (e == hipSuccess) {
+        if (ev0) hipEventRecord(ev0, sc->stream);
+        rc = xgm_launch_filter_mark_query_batch(idx->view, pgs.data(), d_pgs, n_plans, n_padded, under ? under->d_bits : nullptr, (uint32_t*)d_mem, d_count, sc->stream, &n_items, &grid);
+        if (ev1) hipEventRecord(ev1, sc->stream);
+        if (rc) { hipStreamSynchronize(sc->stream); hipFree(d_mem); return rc; }
+        if (ev0) idx->last_kernel = "xgm_filter_mark_query_batch_kernel";
+        e = hipMemcpyAsync(hb, d_count, count_bytes, hipMemcpyDeviceToHost, sc->stream);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(sc->stream);
+    if (e != hipSuccess) { hipStreamSynchronize(sc->stream); hipFree(d_mem); return xgm_launch_error("xgm_filter_mark_query_batch_kernel", (int)e, hipGetErrorString(e)); }
+    FilterBatchHold* hold = new FilterBatchHold();
+    hold->d_mem = d_mem;
+    hold->refs.store(n_plans, std::memory_order_relaxed);
+    for (uint32_t i = 0; i < n_plans; ++i) {
+        xgm_filter* flt = new xgm_filter();
+        flt->device = idx->device; flt->lastdocid = idx->hdr.lastdocid;
+        flt->n_words = n_words; flt->n_words_padded = n_padded;
+        flt->d_bits = (uint32_t*)d_mem + (size_t)i * n_padded; flt->n_docs = h_count[(size_t)i * XGM_FQ_COUNT_STRIDE];
+        flt->hold = hold;
+        if (n_docs) n_docs[i] = flt->n_docs;
+        out[i] = flt;
+    }
+    t_filter_batch_info[0] = 1; t_filter_batch_info[1] = n_items; t_filter_batch_info[2] = grid; t_filter_batch_info[3] = h_count[(size_t)n_plans * XGM_FQ_COUNT_STRIDE];
+    return XGM_OK;
 }
 
 /* ---- the live set; MatchAll and the complement (include/xgm.h: xgm_filter_all, XGM_FILTER_NOT, xgm_index_attach_live) --------------------

@@ -91,6 +91,18 @@ struct xgm_filter_program {
 };
 int xgm_launch_filter_mark_query(const xgm_seg_dev& seg, const xgm_filter_program& pg, uint32_t n_words_padded, uint32_t* bits, unsigned long long* count,
                                  hipStream_t stream);
+/* n_plans (1 .. XGM_FQ_BATCH_MAX = XGM_FILTER_BATCH_MAX of include/xgm.h) such programs in ONE launch (xgm_filter_mark_query_batch_kernel): pgs_dev is
+ * the device copy of pgs_host, which is validated entry by entry as the single launch validates its program; bitmap i goes to
+ * bits + i * n_words_padded, its set bits to count[i * XGM_FQ_COUNT_STRIDE]; under (device, n_words_padded words, or NULL) is ANDed into every
+ * bitmap, and the work items (a unit of one plan) that were skipped because no document of theirs passes it are counted in
+ * count[n_plans * XGM_FQ_COUNT_STRIDE] — count is (n_plans + 1) * XGM_FQ_COUNT_STRIDE words of 64 bits, zeroed by the caller: one counter per
+ * 128-byte line.  *n_items_out / *grid_out (may be NULL) = the work items and the workgroups (one wave each) launched. */
+#define XGM_FQ_BATCH_MAX 64u
+#define XGM_FQ_COUNT_STRIDE 16u
+static_assert(sizeof(xgm_filter_program) == 136, "the batch's program array: 136 bytes per plan");
+int xgm_launch_filter_mark_query_batch(const xgm_seg_dev& seg, const xgm_filter_program* pgs_host, const xgm_filter_program* pgs_dev, uint32_t n_plans,
+                                       uint32_t n_words_padded, const uint32_t* under, uint32_t* bits, unsigned long long* count, hipStream_t stream,
+                                       uint32_t* n_items_out, uint32_t* grid_out);
 /* the live set (xgm_filter_live.h): the same bitmap, the same padding and the same count for doclen[d] != 0 over the u32 doclen section
  * [lastdocid + 1] — the caller compares *count with the header's doccount and keeps the bits only when they agree — or, with all set, for every
  * docid 1 .. lastdocid (doclen is then not read and may be NULL) */

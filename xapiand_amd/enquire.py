@@ -269,6 +269,18 @@ class Database:
         _lib.check(_lib.lib().xgm_filter_build_query(self._h, C.byref(planned), C.byref(h), C.byref(nd)))
         return Filter(h, nd.value, (self._info.lastdocid + 32) // 32, self)
 
+    def build_query_filters(self, plans, under=None):
+        """xgm_filter_build_query_batch: the match sets of 1 .. _lib.XGM_FILTER_BATCH_MAX planned, non-positional queries, each ANDed with the
+        Filter `under` (None: as they are), in one launch → [Filter], one per plan in the plans' order.  All or nothing: the first plan that is
+        declined raises, and nothing is built.  The filters share one device allocation, which is returned when the last of them is closed; each
+        closes on its own."""
+        n = len(plans)
+        arr = (_lib.Query * max(1, n))(*plans)
+        hs, nd = (C.c_void_p * max(1, n))(), (C.c_uint64 * max(1, n))()
+        _lib.check(_lib.lib().xgm_filter_build_query_batch(self._h, arr, n, under._h if under is not None else None, hs, nd))
+        n_words = (self._info.lastdocid + 32) // 32
+        return [Filter(C.c_void_p(hs[i]), nd[i], n_words, self) for i in range(n)]
+
     def filter_all(self):
         """xgm_filter_all: Query::MatchAll as a filter — the index's live set, one bit per docid that exists → Filter (n_docs == doccount).
         Unsupported when the shard has deletions AND live documents of length 0 and no live set is attached (attach_live)."""
