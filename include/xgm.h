@@ -925,6 +925,10 @@ const char* xgm_last_kernel_name(const xgm_index*);
  * bench.py turns these into roofline.model_min_bytes. */
 #define XGM_TRAFFIC_FIELDS 10
 int xgm_last_batch_traffic(xgm_index*, uint64_t* out, uint32_t n);
+/* ... and the bitmap words of [0] that the batch's plain dense units did NOT ask for: their loads of plan terms 2 and 3 are masked by the AND of terms 0 and 1
+ * (DESIGN.md §11.8), 4 words per masked lane and term.  [0] keeps its meaning — the words a stripe's AND is made of —, so the bytes streamed are at most
+ * 4 x ([0] - *words); at which granularity memory serves a partly masked load is a measurement (FETCH_SIZE), not this count.  0 with XGM_NO_STAGED_BITMAPS; an error when the last batch did not run the tallying instantiation. */
+int xgm_last_batch_bitmap_skipped(xgm_index*, uint64_t* words);
 
 /* Algorithmic bytes of a planned query on this shard, SURVEY.md §8(d):
  * Σ_t df_t·8 + S·4 (+ P·4) + k·16, with S and P taken from the last executed result header

@@ -72,6 +72,16 @@ def main():
     for name, (s, l) in out.items():
         print("%-33s: %.2f M probe sectors, %.2f M lanes ask" % (name, s / 1e6, l / 1e6))
     print("planes streamed on crowded stripes: %.2f M sectors" % (heavy[d].sum() * scale * T * (W / 8 / 64) / 1e6))
+    # The staged bitmap loads: the plan is ascending in df, the third term's words are asked for only where the AND of the two rarest
+    # terms holds a document.  A document holds both with probability p01 (averaged over the lengths); a run of g documents is empty with (1 - p01)^g.
+    order = np.argsort(df_stripe, axis=1)                              # rarest first
+    pres = np.take_along_axis(present, order[:, :, None], axis=1)
+    p01 = (pres[:, 0, :] * pres[:, 1, :]).mean(axis=1)
+    print("staged loads, the third term's bitmap of the dense queries' stripes (%.1f MB a launch):" % (d.sum() * scale * (W / 8) / 1e6))
+    for g, what in ((128, "lanes' 16 bytes masked"), (512, "64-byte sectors empty"), (1024, "128-byte groups empty")):
+        empty = (1.0 - p01) ** g                                       # [query]
+        n = empty[d].sum() * scale * (W / g)
+        print("  %-24s: %.2f M (%.0f %%), %.1f MB" % (what, n / 1e6, 100.0 * empty[d].mean(), n * g / 8 / 1e6))
 
 
 if __name__ == "__main__":

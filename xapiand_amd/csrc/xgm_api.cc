@@ -231,7 +231,7 @@ static void fill_view(xgm_index* idx) {
     v.stripe_bits = idx->hdr.stripe_bits;
     v.lastdocid = idx->hdr.lastdocid;
     v.dense_id = nullptr; v.dense_dir = nullptr; v.dense_data = nullptr; v.n_dense = 0; v.dense_pos = 0; v.dense_plane = 0;
-    v.dense_p2 = nullptr; v.bit_screen = 0; v.exact_wdf = 0; v.dense_wdf0 = nullptr; v.reserved_ = 0;
+    v.dense_p2 = nullptr; v.bit_screen = 0; v.exact_wdf = 0; v.dense_wdf0 = nullptr; v.staged_bitmaps = 0; v.reserved_ = 0;
     v.doclen_narrow = nullptr; v.doclen_narrow_bits = 0; v.doclen_base = 0;
     v.flat_off = nullptr; v.flat_did = nullptr; v.flat_wdf = nullptr; v.flat_pos = nullptr;
     v.n_stripes = (idx->hdr.lastdocid >> idx->hdr.stripe_bits) + 1u;
@@ -1175,6 +1175,13 @@ static int run_class_batch(xgm_index* idx, XgmScratch* s, hipStream_t stream, co
     if ((rc = next_event_pair(idx, &pe0, &pe1))) return rc;
     idx->last_kernel = all ? "xgm_andw_all_kernel" : list ? "xgm_andw_list_kernel" : dense ? "xgm_dense_kernel" : bp.andw ? "xgm_andw_kernel" : bp.orw2 ? "xgm_orw2_kernel" : bp.orw ? "xgm_orw_kernel" : bp.and_only ? "xgm_and_kernel" : "xgm_match_kernel";
     idx->last_ghdr = s->d_ghdr; idx->last_n_work = bp.n_work;        /* xgm_last_batch_traffic */
+    idx->last_tallied = idx->tally;                                  /* (the slots below describe this batch, or no batch at all) */
+    if (idx->tally) {                                                /* xgm_last_batch_bitmap_skipped: which headers belong to plain dense units */
+        idx->last_staged_slots.clear();
+        if (mode == 0 && bp.andw && !bp.phrase)
+            for (uint32_t i = 0; i < bp.n_work; ++i)
+                if (h_dq[bp.work[i].qi].flags & XGM_QF_DENSE) idx->last_staged_slots.push_back(bp.work[i].slot);
+    }
     if (bp.orw || (bp.andw && bp.phrase)) {
         if (!hist_zeroed) {
             const size_t n_hist = list ? (size_t)bp.n_work : (size_t)nq * XGM_OR_HIST;
@@ -3715,6 +3722,24 @@ extern "C" int xgm_last_batch_traffic(xgm_index* idx, uint64_t* out, uint32_t n)
         t[8] += g.c_probes_raw; t[9] += g.c_doclen_raw;
     }
     for (uint32_t i = 0; i < n && i < XGM_TRAFFIC_FIELDS; ++i) out[i] = t[i];
+    return XGM_OK;
+}
+
+/* ... and the bitmap words among out[0] that the batch's plain dense units did not ask for (the staged loads of xgm_dense_unit: c_pad[0] of their headers).
+ * Same conditions as xgm_last_batch_traffic; a batch without such units reports 0. */
+extern "C" int xgm_last_batch_bitmap_skipped(xgm_index* idx, uint64_t* words) {
+    if (!idx || !words) return xgm_set_error(XGM_E_INVALID, "null argument");
+    if (!idx->last_ghdr || idx->last_n_work == 0) return xgm_set_error(XGM_E_INVALID, "no batch has run on this index");
+    if (!idx->last_tallied) return xgm_set_error(XGM_E_INVALID, "the last batch did not run the tallying instantiation");
+    int rc = use_device(idx->device);
+    if (rc) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    std::vector<xgm_group_hdr> h(idx->last_n_work);
+    HIP_TRY(hipMemcpy(h.data(), idx->last_ghdr, h.size() * sizeof(xgm_group_hdr), hipMemcpyDeviceToHost));
+    uint64_t sum = 0;
+    for (uint32_t slot : idx->last_staged_slots)
+        if (slot < h.size()) sum += h[slot].c_pad[0];
+    *words = sum;
     return XGM_OK;
 }
 

@@ -270,7 +270,7 @@ int xgm_build_dense(xgm_index* idx) {
 static int build_containers(xgm_index* idx) {
     idx->view.dense_id = nullptr; idx->view.dense_dir = nullptr; idx->view.dense_data = nullptr;
     idx->view.n_dense = 0; idx->view.dense_plane = 0; idx->view.dense_p2 = nullptr; idx->view.bit_screen = 0;
-    idx->view.exact_wdf = 0; idx->view.dense_wdf0 = nullptr; idx->view.reserved_ = 0;
+    idx->view.exact_wdf = 0; idx->view.dense_wdf0 = nullptr; idx->view.staged_bitmaps = 0; idx->view.reserved_ = 0;
     if (idx->d_dense_p2) { hipFree(idx->d_dense_p2); idx->d_dense_p2 = nullptr; }
     if (idx->d_dense_wdf0) { hipFree(idx->d_dense_wdf0); idx->d_dense_wdf0 = nullptr; }
     idx->term_wdfmax.clear();
@@ -359,6 +359,8 @@ static int build_containers(xgm_index* idx) {
     idx->view.dense_wdf0 = (const uint32_t*)idx->d_dense_wdf0;
     /* A/B switch XGM_NO_EXACT_WDF: crowded stripes keep to the summary.  The candidate ring carries the plane bits above a unit-relative docid of 5 + SB bits */
     idx->view.exact_wdf = (!getenv("XGM_NO_EXACT_WDF") && idx->d_dense_wdf0 && idx->d_dense_p2 && plane_off && 5u + SB <= 28u) ? 1u : 0u;
+    /* A/B switch XGM_NO_STAGED_BITMAPS: every lane of a plain dense unit asks for the bitmap words of every term < T, as before the two-stage loads */
+    idx->view.staged_bitmaps = getenv("XGM_NO_STAGED_BITMAPS") ? 0u : 1u;
     idx->dense_min_df = (uint64_t)min_avg * n_stripes;
     hipFree(d_terms); hipFree(d_cnt); hipFree(d_wmax);
     return XGM_OK;

@@ -79,6 +79,7 @@ __host__ __device__ constexpr size_t dense_wave_bytes(bool phrase, uint32_t term
 }
 
 typedef uint32_t dense_u4 __attribute__((ext_vector_type(4)));
+struct dense_u4x2 { dense_u4 a, b; };      /* the two bitmaps a stage of xgm_dense_unit's staged loads asks for */
 
 /* LIST instantiations (xgm_device.h, xgm_prefix_entry): the unit's first matches in docid order, each with its successor in the conjunction.
  * Wave-uniform state; emit() is handed the documents of the conjunction 64 at a time, in docid order by lane, after their positional test. */
@@ -277,6 +278,7 @@ __device__ __forceinline__ void xgm_dense_unit(const xgm_seg_dev& seg, const xgm
 
     /* traffic tallies (xgm_group_hdr), wave-uniform */
     uint32_t cn_bmpw = 0, cn_probe = 0, cn_dl = 0, cn_aux = 0, cn_probe_raw = 0, cn_dl_raw = 0, q_cands = 0;
+    uint32_t cn_skip = 0;                                          /* plain: bitmap words of cn_bmpw that the staged loads did NOT ask for (c_pad[0]) */
     unsigned long long cn_pos = 0;
     auto tally_sectors = [&](bool valid, uint32_t key, uint32_t sh) {
         const uint32_t prev = (uint32_t)__shfl_up((int)key, 1);
@@ -422,6 +424,39 @@ __device__ __forceinline__ void xgm_dense_unit(const xgm_seg_dev& seg, const xgm
         }
         if (TALLY) { cn_bmpw += T * NW; }
         return a;
+    };
+    /* Plain conjunctions load a stripe's bitmaps in TWO STAGES (xgm_seg_dev::staged_bitmaps).  The plan is ascending in df: once its two rarest terms are
+     * ANDed most of a stripe is empty, and the later terms' words are asked for only by the lanes whose own 128 documents still hold a bit of that AND —
+     * an exec-masked load, no address formed in the other lanes, nothing requested when the AND is empty across the wave.  A term index >= T issues no
+     * load at all (the branch is wave-uniform); the loads of a stage go out back to back and are waited for once.  Registers that receive nothing hold
+     * ones: the AND is defined, and zero wherever the first stage's is.  The stages return their two vectors by value and every load stands under a
+     * condition of its own: destinations handed in by reference, or a branch on T around a pair of loads, let the compiler merge the branches' loads
+     * into one block with a selected destination — the bitmaps then live in scratch behind a vmcnt(0). */
+    const dense_u4 kOnes = dense_u4{0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+    bool staged = false;
+    if constexpr (!PHRASE) staged = rfl32(seg.staged_bitmaps) != 0u;
+    auto stage1 = [&](uint32_t x) {                                /* terms 0 and 1 of local stripe x, every lane */
+        /* (the lanes beyond the bitmap keep a zero and ask for nothing — load_words has them read lane 0's words again and then selects, and that
+         *  select is a use: the wave waited for the loads where it had issued them) */
+        dense_u4x2 r;
+        r.a = dense_u4{0u, 0u, 0u, 0u}; r.b = kOnes;
+        const bool in = lane * 4u < NW;
+        const uint32_t o0 = off_of(0u, x), o1 = off_of(1u, x);    /* (read off the lanes' registers by the whole wave, outside the masked blocks) */
+        if (in) r.a = reinterpret_cast<const dense_u4*>(seg.dense_data + (size_t)o0 * 16)[lane];
+        if (T >= 2u && in) r.b = reinterpret_cast<const dense_u4*>(seg.dense_data + (size_t)o1 * 16)[lane];
+        if (TALLY) { cn_bmpw += T * NW; }                         /* (what the stripe's AND is made of: the words stage 2 does not ask for are counted apart, cn_skip) */
+        return r;
+    };
+    auto stage2 = [&](uint32_t x, const dense_u4 a01) {            /* terms 2 and 3 under the AND of terms 0 and 1 */
+        dense_u4x2 r;
+        r.a = kOnes; r.b = kOnes;
+        const bool in = lane * 4u < NW;
+        const bool want = in && (!staged || (a01.x | a01.y | a01.z | a01.w) != 0u);
+        const uint32_t o2 = off_of(2u, x), o3 = off_of(3u, x);
+        if (T >= 3u && want) r.a = reinterpret_cast<const dense_u4*>(seg.dense_data + (size_t)o2 * 16)[lane];
+        if (T >= 4u && want) r.b = reinterpret_cast<const dense_u4*>(seg.dense_data + (size_t)o3 * 16)[lane];
+        if (TALLY) { if (T >= 3u) cn_skip += 4u * (T - 2u) * (uint32_t)__popcll(__ballot(in && !want)); }
+        return r;
     };
 
     /* top-k buffer: room for a round of insertions (bitonic selection when it fills; positional pruning wants its threshold as
@@ -770,10 +805,35 @@ __device__ __forceinline__ void xgm_dense_unit(const xgm_seg_dev& seg, const xgm
     uint32_t sl = next_q(0);
     dense_u4 m = dense_u4{0u, 0u, 0u, 0u}, m_next = dense_u4{0u, 0u, 0u, 0u};
     uint32_t sl_next = n_local;
-    if (sl < n_local) {
-        m = load_and(sl);
-        sl_next = next_q(sl + 1u);
-        if (sl_next < n_local) m_next = load_and(sl_next);
+    /* plain: the pipeline is one stage deeper, since stage 2 depends on stage 1.  While stripe sl is enumerated, stage 2 of the next qualifying stripe
+     * (sl_next: its stage-1 AND in m_next, the later terms' words in n2, n3) and stage 1 of the one after it (sl_s1: f0, f1) are in flight; an advance
+     * shifts: m <- m_next & n2 & n3, stage 2 goes out for what was stage 1, stage 1 for the following next_q stripe. */
+    dense_u4 n2 = kOnes, n3 = kOnes, f0 = dense_u4{0u, 0u, 0u, 0u}, f1 = dense_u4{0u, 0u, 0u, 0u};
+    uint32_t sl_s1 = n_local;
+    (void)n2; (void)n3; (void)f0; (void)f1; (void)sl_s1; (void)load_and; (void)stage1; (void)stage2;
+    auto shift_in = [&]() {                                        /* plain: f0, f1 hold the arrived stage 1 of sl_next — its stage 2, and stage 1 of the stripe after it */
+        m_next = f0 & f1;
+        const dense_u4x2 r = stage2(sl_next, m_next);
+        n2 = r.a; n3 = r.b;
+        sl_s1 = next_q(sl_next + 1u);
+        if (sl_s1 < n_local) { const dense_u4x2 f = stage1(sl_s1); f0 = f.a; f1 = f.b; }
+    };
+    if constexpr (PHRASE) {
+        if (sl < n_local) {
+            m = load_and(sl);
+            sl_next = next_q(sl + 1u);
+            if (sl_next < n_local) m_next = load_and(sl_next);
+        }
+    } else {
+        if (sl < n_local) {                                        /* prologue: units of 1, 2 and 3 qualifying stripes fill the pipeline as far as they go */
+            const dense_u4x2 e = stage1(sl);
+            sl_next = next_q(sl + 1u);
+            if (sl_next < n_local) { const dense_u4x2 f = stage1(sl_next); f0 = f.a; f1 = f.b; }
+            m = e.a & e.b;
+            const dense_u4x2 l = stage2(sl, m);
+            if (sl_next < n_local) shift_in();
+            m &= l.a & l.b;
+        }
     }
     uint32_t o = 0u, o1 = 0u, o2 = 0u, o3 = 0u, n_total = 0u, done = 0u, tail = 0u;       /* (o1..o3: word-major only) */
     bool fresh = true;                                             /* m holds a stripe whose bits have not been counted yet */
@@ -917,11 +977,18 @@ __device__ __forceinline__ void xgm_dense_unit(const xgm_seg_dev& seg, const xgm
             if (TALLY) { q_cands += take_n; }
             done = lim;
             if (done == n_total) {
-                sl = sl_next;
-                m = m_next;
-                if (sl < n_local) {
-                    sl_next = next_q(sl + 1u);
-                    if (sl_next < n_local) m_next = load_and(sl_next);
+                if constexpr (PHRASE) {
+                    sl = sl_next;
+                    m = m_next;
+                    if (sl < n_local) {
+                        sl_next = next_q(sl + 1u);
+                        if (sl_next < n_local) m_next = load_and(sl_next);
+                    }
+                } else {
+                    sl = sl_next;
+                    m = m_next & n2 & n3;                          /* (requested an advance ago) */
+                    sl_next = sl_s1;
+                    if (sl_next < n_local) shift_in();
                 }
                 fresh = true;
             }
@@ -979,6 +1046,7 @@ __device__ __forceinline__ void xgm_dense_unit(const xgm_seg_dev& seg, const xgm
         h.t_start = t_unit_start; h.t_end = __builtin_readcyclecounter();
         h.c_pos = cn_pos; h.c_bmp_words = cn_bmpw; h.c_probes = cn_probe; h.c_blk_words = 0; h.c_hdrs = 0;
         h.c_doclen = cn_dl; h.c_aux_words = cn_aux; h.c_probes_raw = cn_probe_raw; h.c_doclen_raw = cn_dl_raw; h.c_pad[0] = 0; h.c_pad[1] = 0;
+        if (!PHRASE && TALLY) h.c_pad[0] = cn_skip;                  /* (xgm_last_batch_bitmap_skipped; the ALL form has no tallying instantiation) */
         if (ALL) { h.matches = al.n; h.c_pad[0] = al.c; h.c_pad[1] = al.overflow ? XGM_ALL_OVERFLOW : 0u; }
 #ifdef XGM_DENSE_CLOCKS
         h.c_pad[0] = ck_p; h.c_pad[1] = ck_i; h.c_pos = (unsigned long long)(ck_w - ck_s_in) | ((unsigned long long)ck_s << 32);

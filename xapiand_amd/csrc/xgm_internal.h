@@ -116,6 +116,8 @@ struct xgm_index {
     const char* last_kernel = "";      /* diagnostics: which match kernel the last batch used */
     void* last_ghdr = nullptr;         /* device: per-unit summaries of the last batch (xgm_last_batch_traffic) */
     uint32_t last_n_work = 0;
+    bool last_tallied = false;         /* the last batch ran the tallying instantiation: last_staged_slots is its */
+    std::vector<uint32_t> last_staged_slots;   /* tallying launches: the header slots of the batch's plain dense units (xgm_last_batch_bitmap_skipped: c_pad[0] is theirs alone) */
     std::vector<std::pair<void*, void*>> prof_events;   /* hipEvent_t pairs around the match kernel */
     size_t prof_used = 0;
     std::mutex scratch_mu;

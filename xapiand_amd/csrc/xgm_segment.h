@@ -127,7 +127,9 @@ typedef struct {
     /* One word per dense term (built with the containers): non-zero iff the term holds a posting of wdf 0 (a boolean posting: its byte reads 1).  A clear
      * bits2 bit says wdf 0 or 1; only for a term WITHOUT such a posting does it say wdf = 1.  NULL: none, exact_wdf is then 0. */
     const uint32_t* dense_wdf0;
-    unsigned long long reserved_;   /* (the view stays a multiple of 16 bytes: the kernels' arguments behind it keep their alignment) */
+    uint32_t staged_bitmaps;        /* xgm_dense_unit, plain conjunctions: the bitmaps of plan terms 2 and 3 are asked for only by the lanes whose 128 documents hold a
+                                       bit of terms 0 AND 1 (0: every lane asks for every term; XGM_NO_STAGED_BITMAPS) */
+    uint32_t reserved_;             /* (the view stays a multiple of 16 bytes: the kernels' arguments behind it keep their alignment) */
 } xgm_seg_dev;
 
 #define XGM_DENSE_MIN_AVG 32u          /* postings per stripe (on average) that make a term dense     */
