@@ -1012,10 +1012,21 @@ double xgm_debug_concurrent_searches(xgm_index*, const xgm_query_desc* descs, co
 int xgm_debug_phase_cycles(unsigned long long* out8);
 int xgm_debug_merge_cycles(unsigned long long* out8);
 int xgm_debug_orw_phase_cycles(unsigned long long* out8);
-/* The work units plan_batch would cut a batch into (tests/test_batch_plan.py), the disjunction's threshold seed and weight bounds
+/* The work units xgm_plan_batch would cut a batch into (tests/test_batch_plan.py), the disjunction's threshold seed and weight bounds
  * (tests/test_planner.py), and the last batch's per-unit cycle records (tools/units.py). */
 int64_t xgm_debug_plan_batch(const xgm_index*, const xgm_query* qs, uint32_t nq, char* kernel, uint32_t* units, uint64_t cap);
 int xgm_debug_or_bounds(const xgm_index*, const xgm_query* q, double* seed, double* ub, double* ub1);
+/* Host only: pretend acceleration structures on an XGM_DEVICE_NONE index (XGM_E_INVALID on an index that has a device), so that the
+ * planner's whole decision space is reachable without a GPU.  flags: 1 probe containers, 2 flat posting arrays, 4 containers with
+ * position bases, 8 flat arrays with position offsets; dense_min_df: the termfreq from which a term has containers. */
+int xgm_debug_set_plan_facts(xgm_index* idx, uint64_t dense_min_df, uint32_t flags, uint64_t flat_postings);
+/* Host only: the complete plan of a batch.  mode 0 a search, 1 the LIST launch, 2 the COUNT launch; force_general: the workgroup kernel's
+ * decomposition.  out[0] the planner's return code (the rest zero unless XGM_OK); out[1..20] nq, k_max, tab_terms, n_work,
+ * stripes_per_group, cap, k_stride_c, merge_cap, phrase, wide, and_only, andw, sided, orw, fused, parts, sub_bits, orw_planes, orw2,
+ * or_flat; out[21..25] FNV-1a 64 of the device queries' bytes, of k per query, of max_possible per query, of the slot offsets and of the
+ * work list's bytes.  Then, as far as cap (>= 26) allows, every device query's flags (nq words) and (qi, s_begin, s_end, slot) of every
+ * work unit in launch order.  Returns the words of the whole dump (tools/plan_dump.py). */
+int64_t xgm_debug_plan_dump(const xgm_index*, const xgm_query* qs, uint32_t nq, uint32_t mode, uint32_t force_general, uint64_t* out, uint32_t cap);
 int64_t xgm_debug_last_units(xgm_index*, unsigned long long* out, uint64_t cap);
 int64_t xgm_debug_last_units2(xgm_index*, unsigned long long* out, unsigned long long* out_pos, uint64_t cap);
 

@@ -318,7 +318,7 @@ def test_enquire_mirror_against_the_references_own_msets(built, tmp_path):
 
 
 def test_single_sorted_search_of_a_plan_in_parts(built, tmp_path):
-    """A query whose units exceed one merge's capacity is planned in parts (plan_batch: pseudo-query p * nq + q of the unit offsets).  The
+    """A query whose units exceed one merge's capacity is planned in parts (xgm_plan_batch: pseudo-query p * nq + q of the unit offsets).  The
     single sorted search walks the units of every part and answers; the batch entry point declines such a plan, for one query too.
     No diagnostic shows the sorted plan, so that it has more than one part is derived here from the planner's constants: a unit's run table
     (16 KiB, 8 B per term and stripe) holds at most 16384 / (8 * 16) = 128 stripes of a 16-term query — fewer where the LDS is tight —, one

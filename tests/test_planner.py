@@ -132,7 +132,7 @@ def test_static_match_bounds_equal_the_references(built, tmp_path):
 
 
 def test_disjunction_threshold_guess_is_conservative(built, tmp_path):
-    """The planner's guess of a disjunction's final k-th weight (xgm_dev_query::theta_seed, xgm_api.cc or_theta_seed) only steers
+    """The planner's guess of a disjunction's final k-th weight (xgm_dev_query::theta_seed, xgm_batch_plan.cc or_theta_seed) only steers
     which documents the kernel weighs first — but it earns its keep only if it is (a) rarely above the true k-th weight (then the
     kernel must go round again) and (b) not far below it.  On the synthetic corpus: never above, and within a factor of two."""
     import ctypes as C
@@ -157,7 +157,7 @@ def test_disjunction_threshold_guess_is_conservative(built, tmp_path):
 
 def test_disjunction_term_bounds_dominate_every_posting(built, tmp_path):
     """xgm_orw_kernel may skip a document only because a sum of per-term bounds stays below the running k-th weight, so the bounds
-    the planner hands it (xgm_dev_query::ub — any wdf; ub1 — wdf = 1; xgm_api.cc to_dev_query) must dominate the BM25 weight
+    the planner hands it (xgm_dev_query::ub — any wdf; ub1 — wdf = 1; xgm_batch_plan.cc to_dev_query) must dominate the BM25 weight
     (bm25weight.cc:170-181) of EVERY posting of the term.  Checked exhaustively over the postings of sampled terms, for the default
     parameters and for b = 0 / k1 = 0 / a large min_normlen, where the length normalisation degenerates."""
     import ctypes as C

@@ -39,7 +39,7 @@ def close(self):
         print("UNITS cycles/stripe mean", (dur / np.maximum(1, stripes)).mean(), "stripes/unit mean,max", stripes.mean(), stripes.max())
         print("UNITS matches", int(a[:, 6].sum()), "documents weighed (xgm_orw_kernel only)", int(a[:, 7].sum()),
               "ratio", float(a[:, 7].sum()) / max(1.0, float(a[:, 6].sum())))
-        # least-squares fit of the unit time: cycles = a * stripes + b * matches + c (the planner's cost model, xgm_api.cc)
+        # least-squares fit of the unit time: cycles = a * stripes + b * matches + c (the planner's cost model, xgm_batch_plan.cc)
         A = np.stack([stripes, a[:, 6].astype(np.float64), np.ones(n)], axis=1)
         coef, *_ = np.linalg.lstsq(A, dur, rcond=None)
         print("UNITS fit cycles = %.1f * stripes + %.2f * matches + %.0f; residual rms %.0f" % (coef[0], coef[1], coef[2], float(np.sqrt(((A @ coef - dur) ** 2).mean()))))

@@ -15,6 +15,7 @@
 #include <cstring>
 #include <string>
 
+#include "xgm_batch_plan.h"
 #include "xgm_filter_hold.h"
 #include "xgm_internal.h"
 #include "xgm_launch.h"
@@ -524,516 +525,15 @@ extern "C" uint64_t xgm_query_postings_bytes(const xgm_index* idx, const xgm_que
 
 /* ------------------------------------------------------------------ search ------------------- */
 
-static uint32_t next_pow2(uint32_t v) {
-    uint32_t p = 1;
-    while (p < v) p <<= 1;
-    return p;
-}
-
-/* A first guess of a disjunction's final k-th weight (xgm_dev_query::theta_seed).  A document that indexes exactly the terms S weighs at
- * least wlow(S) = Σ_{t in S} weight(wdf = 1, the longest document) — BM25 is monotone in both.  With independent terms N · Π p_t · Π (1 - p_t)
- * documents match exactly S; the guess is the largest wlow(S) such that the subsets at or above it are expected to hold a few times k
- * documents.  It only steers which documents are weighed first: xgm_orw_kernel weighs everything whose BOUND reaches the guess and, should
- * fewer than k of those reach it (correlated terms, tiny shards), goes round again below it. */
-static double or_theta_seed(const xgm_index* idx, const xgm_query* q, const xgm_dev_query* d) {
-    struct Tm { double p, wlow, ub; };
-    Tm tm[XGM_MAX_TERMS];
-    uint32_t n = 0;
-    const double N = (double)idx->hdr.doccount;
-    const double nl_ub = std::max((double)idx->hdr.doclen_upper_bound * q->len_factor, q->min_normlen);
-    const double denom_max = q->k1 * (nl_ub * q->b + (1.0 - q->b));
-    for (uint32_t t = 0; t < q->n_terms; ++t) {
-        const uint32_t id = q->terms[t].term_id;
-        if (id == UINT32_MAX || !(q->terms[t].termweight > 0.0)) continue;
-        tm[n++] = Tm{std::min(1.0, (double)idx->term_df[id] / N), q->terms[t].termweight * (1.0 / (denom_max + 1.0)), d->ub[t]};
-    }
-    if (n == 0) return 0.0;
-    std::sort(tm, tm + n, [](const Tm& a, const Tm& b) { return a.ub > b.ub; });
-    if (n > 8u) n = 8u;                     /* the eight terms with the largest bounds; whatever else a document indexes only adds weight */
-    std::pair<double, double> sub[256];     /* (wlow, expected documents) */
-    const uint32_t ns = 1u << n;
-    for (uint32_t S = 1; S < ns; ++S) {
-        double p = N, w = 0.0;
-        for (uint32_t i = 0; i < n; ++i) { if ((S >> i) & 1u) { p *= tm[i].p; w += tm[i].wlow; } else p *= 1.0 - tm[i].p; }
-        sub[S - 1] = std::make_pair(w, p);
-    }
-    std::sort(sub, sub + (ns - 1u), [](const std::pair<double, double>& a, const std::pair<double, double>& b) { return a.first > b.first; });
-    const double need = 3.0 * (double)d->k;
-    double acc = 0.0;
-    for (uint32_t i = 0; i + 1u < ns; ++i) { acc += sub[i].second; if (acc >= need) return sub[i].first; }
-    return 0.0;
-}
-
-/* xgm_query → device form; returns the wdf table width the query needs (1 or 2 bytes), 0 if too big */
-static int to_dev_query(const xgm_index* idx, const xgm_query* q, xgm_dev_query* d) {
-    memset(d, 0, sizeof *d);
-    d->op = q->op == XGM_OP_FILTER ? XGM_OP_AND : q->op == XGM_OP_NEAR ? XGM_OP_PHRASE : q->op;   /* a FILTER is a conjunction some of whose leaves weigh
-                                                                                                      nothing; NEAR = PHRASE with another predicate */
-    d->n_terms = q->n_terms;
-    d->k = q->first + q->maxitems;
-    d->window = q->window;
-    d->len_factor = q->len_factor; d->k1 = q->k1; d->b = q->b; d->min_normlen = q->min_normlen;
-    int width = 1;
-    bool any_absent = false, all_absent = true;
-    for (uint32_t t = 0; t < q->n_terms; ++t) {
-        d->term_id[t] = q->terms[t].term_id;
-        d->termweight[t] = q->terms[t].termweight;
-        d->phrase_index[t] = (uint8_t)q->terms[t].phrase_index;
-        if (q->terms[t].term_id == UINT32_MAX) { if (q->op == XGM_OP_OR || ((q->req_mask >> t) & 1u)) any_absent = true; continue; }
-        all_absent = false;
-        if (q->terms[t].term_id >= idx->hdr.n_terms) return -1;
-        uint32_t ub = idx->term_wdfub[q->terms[t].term_id];
-        if (ub > 65534u) return 0;
-        if (ub > 254u) width = 2;
-        /* leaf weight <= termweight * wdf_ub / (k1 * (min_normlen * b + 1 - b) + wdf_ub) <= termweight:
-         * every factor of BM25Weight::get_sumpart is monotone in wdf and in the normalised length */
-        double bound = q->terms[t].termweight, bound1 = bound;
-        const double nl_lb = std::max((double)idx->hdr.doclen_lower_bound * q->len_factor, q->min_normlen);     /* normlen of any document is at least this */
-        const double denom_min = q->k1 * (nl_lb * q->b + (1.0 - q->b));
-        const uint32_t wmax = idx->term_wdfmax.empty() ? ub : std::min(ub, idx->term_wdfmax[q->terms[t].term_id]);   /* the true largest wdf where known */
-        if (wmax > 0 && denom_min > 0) { bound = q->terms[t].termweight * ((double)wmax / (denom_min + (double)wmax)); bound1 = q->terms[t].termweight * (1.0 / (denom_min + 1.0)); }
-        d->ub[t] = bound * 1.000000001;
-        d->ub1[t] = std::min(bound1, bound) * 1.000000001;
-    }
-    if (q->op == XGM_OP_OR && d->k > 0 && idx->hdr.doccount > 0) {
-        /* A/B switch (variant tests): scale the guess — far too high forces the kernel's second pass everywhere, 0 switches it off */
-        static const double seed_scale = getenv("XGM_OR_SEED_SCALE") ? atof(getenv("XGM_OR_SEED_SCALE")) : 1.0;
-        d->theta_seed = or_theta_seed(idx, q, d) * seed_scale;
-    }
-    if ((q->op == XGM_OP_PHRASE || q->op == XGM_OP_NEAR) && q->phrase_active) {
-        d->flags |= XGM_QF_PHRASE;
-        /* Enquire::get_mset's check_at_least (enquire.cc:419-426): beyond the page it asks for more documents to be LOOKED AT so that
-         * the match count is accurate; within it (Xapiand passes 0) the matcher may stop caring about documents that cannot rank */
-        static const bool no_pos_prune = getenv("XGM_NO_POS_PRUNE") != nullptr;         /* A/B switch for measurements */
-        if (!no_pos_prune && q->check_at_least <= q->first + q->maxitems) d->flags |= XGM_QF_POSPRUNE;
-        if (q->replay & XGM_REPLAY_BATCH_COUNT) d->flags |= XGM_QF_COUNT_ALL;       /* (read by xgm_andw_list_kernel's units only) */
-        if (q->op == XGM_OP_NEAR) d->flags |= XGM_QF_NEAR | (idx->near_colocated.load(std::memory_order_relaxed) ? XGM_QF_NEAR_COLOC : 0u);
-        else if (q->window == q->n_terms) d->flags |= XGM_QF_EXACT;
-    }
-    if (q->op == XGM_OP_TREE) {
-        /* a nested query: groups + binary nodes straight from the plan; the match kernel evaluates them per document */
-        if (q->n_groups == 0 || q->n_groups > XGM_MAX_TERMS || q->tree_len > XGM_MAX_TREE || q->tree_root >= q->n_groups + q->tree_len) return -1;
-        d->flags |= XGM_QF_TREE;
-        d->tree_len = q->tree_len; d->n_groups = q->n_groups; d->tree_root = q->tree_root; d->group_scored = q->group_scored;
-        for (uint32_t t = 0; t < q->n_terms; ++t) { if (q->group_of[t] >= q->n_groups) return -1; d->group_of[t] = q->group_of[t]; }
-        for (uint32_t g = 0; g < q->n_groups; ++g) d->termweight[g] = q->group_weight[g];
-        for (uint32_t j = 0; j < q->tree_len; ++j) {
-            if (q->tree_a[j] >= q->n_groups + j || q->tree_b[j] >= q->n_groups + j || q->tree_op[j] < XGM_N_AND || q->tree_op[j] > XGM_N_MAYBE) return -1;
-            d->tnode_op[j] = q->tree_op[j]; d->tnode_a[j] = q->tree_a[j]; d->tnode_b[j] = q->tree_b[j];
-        }
-        d->score_mask = 0; d->req_mask = 0; d->neg_mask = 0; d->n_req = 0;
-        return width;
-    }
-    if (q->op == XGM_OP_OR ? all_absent : any_absent) d->flags |= XGM_QF_EMPTY;
-    /* post-order program → node list */
-    int stack[2 * XGM_MAX_TERMS];
-    int sp = 0, n_nodes = 0;
-    if (q->sum_len == 0 || q->sum_len > 2 * q->n_terms - 1 || (q->sum_len & 1u) == 0) return -1;
-    for (uint32_t i = 0; i < q->sum_len; ++i) {
-        int8_t op = q->sum_prog[i];
-        if (op >= 0) {
-            if ((uint32_t)op >= q->n_terms) return -1;
-            if (q->terms[op].termweight != 0.0) d->score_mask |= 1u << op;   /* a real term's BM25 weight is > 0; 0 marks an unweighted (FILTER) leaf */
-            stack[sp++] = op;
-        } else {
-            if (sp < 2) return -1;
-            int r = stack[--sp], l = stack[--sp];
-            d->node_a[n_nodes] = (uint8_t)l;
-            d->node_b[n_nodes] = (uint8_t)r;
-            stack[sp++] = (int)q->n_terms + n_nodes;
-            ++n_nodes;
-        }
-    }
-    if (sp != 1 || n_nodes != ((int)q->sum_len - 1) / 2) return -1;
-    d->n_nodes = (uint32_t)n_nodes;
-    d->sum_root = (uint32_t)stack[0];
-    d->req_mask = q->req_mask;
-    d->neg_mask = q->neg_mask;
-    d->n_req = (uint32_t)__builtin_popcount(q->req_mask);
-    if (q->op != XGM_OP_OR && (q->req_mask == 0 || (q->req_mask >> q->n_terms) != 0 || (q->req_mask & q->neg_mask))) return -1;
-    {
-        int slot_of[2 * XGM_MAX_TERMS];
-        for (uint32_t t = 0; t < q->n_terms; ++t) slot_of[t] = (int)t;
-        for (int j = 0; j < n_nodes; ++j) {
-            d->ip_a[j] = (uint8_t)slot_of[d->node_a[j]];
-            d->ip_b[j] = (uint8_t)slot_of[d->node_b[j]];
-            slot_of[q->n_terms + j] = slot_of[d->node_a[j]];
-        }
-        d->ip_root = (uint32_t)slot_of[stack[0]];
-    }
-    return width;
-}
-
 /* Diagnostics: nanoseconds the host spent per section of a batch call since the last fetch
- * (xgm_debug_host_ns): [0] xgm_plan_query of the descriptions, [1] plan_batch (device queries, cost model, work
+ * (xgm_debug_host_ns): [0] xgm_plan_query of the descriptions, [1] xgm_plan_batch (device queries, cost model, work
  * list), [2] staging + enqueue (copies, events, launches), [3] batches. */
 static std::atomic<uint64_t> g_host_ns[8];           /* [4..7]: staging memcpys, H2D enqueue + events, match launch, merge launch */
 static inline uint64_t now_ns() { return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 static std::vector<xgm_work> g_last_work;          /* diagnostics only */
 static xgm_group_hdr* g_last_ghdr = nullptr;
 
-struct BatchPlan {
-    uint32_t nq, k_max, tab_terms, n_work, stripes_per_group, cap, k_stride_c, merge_cap;
-    std::vector<xgm_work> work;        /* heaviest first */
-    std::vector<uint32_t> goff;        /* [nq+1] first output slot of each query */
-    bool phrase, wide;
-    bool and_only;      /* every query is a plain conjunction of >= 2 terms → xgm_and_kernel */
-    bool andw;          /* ... and k is small: the wave-autonomous variant (one wave per unit) */
-    int sided;          /* andw batch with right-hand terms: 1 = AND_NOT only, 2 = AND_MAYBE too */
-    bool orw;           /* every query is a plain disjunction → xgm_orw_kernel (one wave per unit) */
-    bool fused = false; /* the conjunction kernel finishes its queries itself (xgm_unit_finish.h): no merge launch, no parts */
-    uint32_t parts = 1; /* > 1: a query's units are merged in `parts` groups (pseudo-query p * nq + q of goff) and the groups' lists once more */
-    uint32_t sub_bits = 0; /* workgroup kernels: every stripe in 2^sub_bits passes over narrower tables (positional queries of > 3 terms) */
-    int orw_planes = 6;    /* orw batch: planes of xgm_orw_kernel's bound sum (4 where every query has 4-8 terms) */
-    int orw2 = 0;          /* orw batch whose every query xgm_orw2_kernel takes: 1 = containers only, 2 = with flat-array terms */
-    bool or_flat = false;  /* orw batch: every term without a container has a flat posting array (xgm_orw_kernel's FLAT instantiation) */
-    /* (a plan that is kept between calls — run_class_batch's, per thread: a work list of tens of thousands of units is a megabyte that would otherwise be
-     *  allocated, faulted in and released per batch) */
-    void reset() { work.clear(); goff.clear(); fused = false; parts = 1; sub_bits = 0; orw2 = 0; orw_planes = 6; or_flat = false; }
-};
-
-static int dense_kind(const xgm_index* idx, const xgm_query& q, bool fused = false);
-static bool flat_kind(const xgm_index* idx, const xgm_query& q);
-static int or2_kind(const xgm_index* idx, const xgm_query& q);
-
-static int plan_batch(const xgm_index* idx, const xgm_query* qs, uint32_t nq, xgm_dev_query* dq, uint32_t* kq, double* maxposs,
-                      BatchPlan* bp, bool force_general = false, int mode = 0) {
-    const bool list = mode == 1;                     /* xgm_andw_list_kernel's launch; mode 2: xgm_andw_all_kernel's (both: one part, no last-unit merge) */
-    bp->nq = nq; bp->k_max = 1; bp->tab_terms = 1; bp->phrase = false; bp->wide = false; bp->and_only = true;
-    bool or_only = getenv("XGM_NO_ORW") == nullptr;                                  /* A/B switch for measurements */
-    bool conj_only = true;       /* every query: AND / PHRASE of >= 2 terms (positional filter or not) */
-    bool andnot_ok = true;       /* every query: AND, AND_NOT or AND_MAYBE whose required terms are plan positions [0, n_req) */
-    static const bool no_and_kernel = getenv("XGM_NO_AND_KERNEL") != nullptr;      /* A/B switch for measurements */
-    if (no_and_kernel) bp->and_only = false;
-    if (force_general) { bp->and_only = false; or_only = false; conj_only = false; andnot_ok = false; }   /* the workgroup kernel's decomposition (xgm_search_sorted) */
-    for (uint32_t i = 0; i < nq; ++i) {
-        if (qs[i].n_terms == 0 || qs[i].n_terms > XGM_MAX_TERMS) return xgm_set_error(XGM_E_INVALID, "query %u: bad n_terms", i);
-        int width = to_dev_query(idx, &qs[i], &dq[i]);
-        if (width < 0) return xgm_set_error(XGM_E_INVALID, "query %u: malformed plan", i);
-        if (width == 0) return XGM_UNSUPPORTED;
-        if (dq[i].k > XGM_MAX_K) return XGM_UNSUPPORTED;
-        if (width == 2) bp->wide = true;
-        if (dq[i].op != XGM_OP_AND || dq[i].n_terms < 2 || (dq[i].flags & XGM_QF_PHRASE)) bp->and_only = false;
-        if (dq[i].op != XGM_OP_OR) or_only = false;
-        if ((dq[i].op != XGM_OP_AND && dq[i].op != XGM_OP_AND_NOT && dq[i].op != XGM_OP_AND_MAYBE) || dq[i].n_terms < 2 ||
-            (dq[i].flags & XGM_QF_PHRASE) || dq[i].req_mask != (dq[i].n_req >= 32u ? 0xFFFFFFFFu : (1u << dq[i].n_req) - 1u) ||
-            (dq[i].op != XGM_OP_AND && dq[i].n_terms > 8u) ||                       /* the wave kernel sums <= 8 leaves in registers */
-            (dq[i].op == XGM_OP_AND_NOT && (dq[i].req_mask | dq[i].neg_mask) != (1u << dq[i].n_terms) - 1u))
-            andnot_ok = false;
-        if ((dq[i].op != XGM_OP_AND && dq[i].op != XGM_OP_PHRASE) || dq[i].n_terms < 2) conj_only = false;
-        if (dq[i].flags & XGM_QF_PHRASE) {
-            if (dq[i].n_terms > XGM_PHRASE_MAX_TERMS) return XGM_UNSUPPORTED;
-            bp->phrase = true;
-        }
-        bp->k_max = std::max(bp->k_max, dq[i].k);
-        bp->tab_terms = std::max(bp->tab_terms, dq[i].n_terms);
-        kq[i] = dq[i].k;
-        maxposs[i] = qs[i].max_possible;
-    }
-    if (bp->phrase && bp->tab_terms > XGM_PHRASE_MAX_TERMS) {
-        /* a batch mixing long AND/OR queries with phrases would blow the LDS budget: caller splits */
-        return XGM_UNSUPPORTED;
-    }
-    static const bool no_andw = getenv("XGM_NO_ANDW") != nullptr;                    /* A/B switch for measurements */
-    const uint32_t n_stripes = (idx->hdr.lastdocid >> idx->hdr.stripe_bits) + 1u;
-    const uint32_t k_pad = next_pow2(bp->k_max);
-    static const bool no_phrase_w = getenv("XGM_NO_PHRASEW") != nullptr;           /* A/B switch for measurements */
-    const bool phrase_conj = conj_only && bp->phrase && !no_phrase_w && !no_and_kernel;
-    if (no_and_kernel) andnot_ok = false;
-    if (!bp->and_only && bp->tab_terms > 8u) andnot_ok = false;      /* a SIDED launch sums every query's leaves in 8 registers */
-    bool any_maybe = false;
-    for (uint32_t i = 0; i < nq; ++i) any_maybe = any_maybe || dq[i].op == XGM_OP_AND_MAYBE;
-    bp->sided = (andnot_ok && !bp->and_only) ? (any_maybe ? 2 : 1) : 0;
-    bp->andw = (bp->and_only || andnot_ok || phrase_conj) && !no_andw && bp->k_max <= 192u && (uint64_t)((n_stripes + 31u) / 32u) * k_pad <= XGM_MERGE_CAP &&
-               xgm_andw_smem_bytes(idx->hdr.stripe_bits, bp->tab_terms, std::max(128u, next_pow2(bp->k_max + 64u)), bp->wide, 32u, bp->phrase, bp->sided == 2) <= 160u * 1024u;
-    /* disjunctions: one wave per unit as well; a unit spans as many stripes as the merge capacity
-     * (units x k candidates per query) requires */
-    uint32_t orw_spg = 32u;
-    while ((uint64_t)((n_stripes + orw_spg - 1u) / orw_spg) * k_pad > XGM_MERGE_CAP && orw_spg < 4096u) orw_spg *= 2u;
-    bp->orw = or_only && (uint64_t)((n_stripes + orw_spg - 1u) / orw_spg) * k_pad <= XGM_MERGE_CAP &&
-              xgm_orw_smem_bytes(idx->hdr.stripe_bits, bp->tab_terms, std::max(128u, next_pow2(bp->k_max + 64u)), bp->wide, orw_spg) <= 160u * 1024u;
-    static const bool no_or_flat = getenv("XGM_NO_OR_FLAT") != nullptr;                 /* A/B switch (the variant tests): block decode for every term without a container */
-    if (bp->orw && !bp->wide && !no_or_flat && idx->view.flat_off && idx->view.n_dense && idx->flat_postings < 0xFFFFFFFFull) {
-        bool all = true;
-        for (uint32_t i = 0; i < nq && all; ++i)
-            for (uint32_t t = 0; t < qs[i].n_terms && all; ++t) {
-                const uint32_t id = qs[i].terms[t].term_id;
-                if (id == UINT32_MAX || (uint64_t)idx->term_df[id] >= idx->dense_min_df) continue;       /* absent, or it has a container */
-                all = idx->term_wdfub[id] <= 254u && idx->term_df[id] != 0;                             /* (what build_flat gives an array) */
-            }
-        bp->or_flat = all;
-    }
-    if (bp->orw) {
-        /* planes of the bound sum (xgm_or.hip, PL): 4 where every query of the batch has 4-8 terms, else 6 (XGM_ORW_PLANES=4 | 6 forces one: A/B, the variant tests) */
-        static const int forced = getenv("XGM_ORW_PLANES") ? atoi(getenv("XGM_ORW_PLANES")) : 0;
-        bool four = true;
-        for (uint32_t i = 0; i < nq && four; ++i) four = qs[i].n_terms >= 4u && qs[i].n_terms <= 8u;
-        bp->orw_planes = forced == 4 || forced == 6 ? forced : (four ? 4 : 6);
-    }
-    if (bp->orw && !bp->wide && bp->tab_terms <= 8u) {
-        int kind = 1;
-        for (uint32_t i = 0; i < nq && kind; ++i) { const int kq_ = or2_kind(idx, qs[i]); kind = kq_ == 0 ? 0 : std::max(kind, kq_); }
-        if (kind && xgm_orw2_smem_bytes(idx->hdr.stripe_bits, bp->tab_terms, std::max(128u, next_pow2(bp->k_max + 64u)), orw_spg, kind == 2) <= 160u * 1024u) bp->orw2 = kind;
-    }
-    const bool wave_units = bp->andw || bp->orw;
-    /* plain conjunctions over containers only: their units take xgm_dense_unit inside xgm_andw_kernel<uint8_t, false, 0> */
-    /* ... and positional queries over containers only that prune by weight: xgm_dense_unit<PHRASE> inside the positional instantiation
-     * (XGM_NO_DENSE_PHRASE_BODY: A/B switch, the variant tests) */
-    static const bool no_dense_phrase = getenv("XGM_NO_DENSE_PHRASE_BODY") != nullptr;
-    if (bp->andw && bp->sided == 0 && !bp->wide)
-        for (uint32_t i = 0; i < nq; ++i) {
-            const int dk = dense_kind(idx, qs[i], true);
-            if ((dk == 1 && !bp->phrase) || (dk == 2 && bp->phrase && !no_dense_phrase && (dq[i].flags & XGM_QF_POSPRUNE))) dq[i].flags |= XGM_QF_DENSE;
-            /* ... or led by a long-tail term with a flat posting array: xgm_flat_unit (positional queries: those that prune by weight) */
-            else if (!(dq[i].flags & XGM_QF_EMPTY) && flat_kind(idx, qs[i]) && (!bp->phrase || (dq[i].flags & XGM_QF_POSPRUNE)) &&
-                     ((qs[i].op == XGM_OP_PHRASE || qs[i].op == XGM_OP_NEAR) ? bp->phrase : !bp->phrase))
-                dq[i].flags |= XGM_QF_FLAT;
-        }
-    /* the bodies live in the first bytes of xgm_andw_kernel's per-wave LDS slice: flagged only where they fit (they do for any batch the
-     * wave kernel takes: its positional slice holds its own staging area of tab_terms x 2 KiB) */
-    if (bp->andw && bp->sided == 0 && !bp->wide) {
-        const size_t slice = xgm_andw_smem_bytes(idx->hdr.stripe_bits, bp->tab_terms, std::max(128u, next_pow2(bp->k_max + 64u)), bp->wide, 32u, bp->phrase, false) / XGM_WAVES;
-        for (uint32_t i = 0; i < nq; ++i) {
-            if ((dq[i].flags & XGM_QF_FLAT) && xgm_body_wave_bytes(true, bp->phrase, dq[i].n_terms) > slice) dq[i].flags &= ~XGM_QF_FLAT;
-            if ((dq[i].flags & XGM_QF_DENSE) && xgm_body_wave_bytes(false, bp->phrase, dq[i].n_terms) > slice) dq[i].flags &= ~XGM_QF_DENSE;
-        }
-    }
-    bp->cap = wave_units ? std::max(128u, next_pow2(bp->k_max + 64u)) : std::max(512u, next_pow2(bp->k_max + XGM_WG));
-    /* Work decomposition.  Cost model of a query: the posting blocks its terms own (df/128 full blocks
-     * plus about one partial block per stripe a term touches).  Every query is cut into units of
-     * about total/(units the chip holds) cost — heavy queries into many — bounded by the LDS run table
-     * (8 B per term and stripe → at most spg_max stripes per unit) and by the merge kernel's sort
-     * capacity (units × k candidates). */
-    uint32_t spg_max = bp->andw ? 32u : bp->orw ? orw_spg : std::max(1u, (16u * 1024u) / (8u * bp->tab_terms));
-    if (!wave_units) {
-        /* the run table shares the 160 KiB with the tables (PHRASE position tables are large) */
-        /* (the sorted instantiation — force_general — keeps a second key, a collapse ordinal and its control words per top-k entry) */
-        const size_t extra = force_general ? (size_t)bp->cap * 12 + 128 : 0;
-        size_t base = xgm_match_smem_bytes(idx->hdr.stripe_bits, bp->tab_terms, bp->phrase, bp->cap, bp->wide, 0) + extra;
-        /* a positional query of more than XGM_PHRASE_MAX_TERMS_WG terms: 4-byte position starts for every slot of a stripe and term do not
-         * fit; the kernel then takes a stripe in 2^sub_bits passes over tables of W >> sub_bits slots (xgm_match_body.inc), leaving room
-         * for a run table of at least 16 stripes */
-        while (bp->phrase && base + 8u * bp->tab_terms * 16u + 64u > 160u * 1024u && bp->sub_bits < 3u && idx->hdr.stripe_bits - bp->sub_bits > 8u) {
-            ++bp->sub_bits;
-            base = xgm_match_smem_bytes(idx->hdr.stripe_bits - bp->sub_bits, bp->tab_terms, bp->phrase, bp->cap, bp->wide, 0) + extra;
-        }
-        if (base + 8u * bp->tab_terms + 64u > 160u * 1024u) return XGM_UNSUPPORTED;
-        spg_max = std::min<uint32_t>(spg_max, (uint32_t)((160u * 1024u - 64u - base) / (8u * bp->tab_terms)));
-    }
-    const uint32_t g_min = (n_stripes + spg_max - 1) / spg_max;
-    /* few queries in flight (latency mode): a smaller merge (sort of <= 4096) beats more units */
-    const uint32_t merge_budget = (nq <= 4u && !bp->orw) ? XGM_MERGE_CAP / 2u : XGM_MERGE_CAP;   /* (a disjunction's units are long: more of them wins) */
-    static const uint32_t units_cap = getenv("XGM_MAX_UNITS_PER_QUERY") ? (uint32_t)atoi(getenv("XGM_MAX_UNITS_PER_QUERY")) : 0u;   /* A/B switch for measurements */
-    /* units x k candidates must fit the merge kernel's LDS sort; a unit's window there is k_max entries (not the next power of two) */
-    static const bool units_by_kpad = getenv("XGM_UNITS_BY_KPAD") != nullptr;                      /* A/B switch: the round-2 bound */
-    /* ... per PART: a query whose units exceed one merge's capacity is merged in up to kMaxParts groups and the groups' lists once more
-     * (xgm_merge_parts), so that the heaviest conjunctions — frequent-term phrases whose every document is a candidate — can be cut
-     * down to single stripes: the launch ends with its longest unit (measured: C5's kernel ran at 20 % mean occupancy behind them) */
-    static const uint32_t kMaxParts = getenv("XGM_MAX_PARTS") ? (uint32_t)std::min(8, std::max(1, atoi(getenv("XGM_MAX_PARTS")))) : 4u;      /* A/B switch (<= 8: the parts' merge sorts parts x k in LDS) */
-    const uint32_t units_per_part = std::max(1u, merge_budget / (units_by_kpad ? k_pad : std::max(1u, bp->k_max)));
-    const uint32_t parts_ok = (bp->andw && nq > 4u) ? kMaxParts : 1u;
-    uint32_t g_max = std::max(g_min, std::min(n_stripes, units_per_part * parts_ok));
-    if (units_cap) g_max = std::max(g_min, std::min(g_max, units_cap));
-    if ((uint64_t)g_min * k_pad > XGM_MERGE_CAP) return XGM_UNSUPPORTED;
-    /* Cost model of a query (unit: ~1k cycles of one wave, measured on MI355X): every
-     * active stripe pays a fixed latency chain; each posting block that still has to be decoded (terms
-     * without probe containers) adds ~1; each candidate costs a probe + a share of the scoring. */
-    std::vector<double> cost(nq), conj_per_stripe(nq, 0.0);
-    double total_cost = 0;
-    const double n_docs = std::max<double>(1.0, idx->hdr.doccount);
-    const double Wd = (double)(1u << idx->hdr.stripe_bits);
-    for (uint32_t i = 0; i < nq; ++i) {
-        double sparse_blocks = 0, min_df = 1e30, dens = 1.0;
-        bool all_dense = bp->andw;
-        uint32_t sparse_req = 0;                     /* required terms without containers */
-        bool sparse_rhs = false;                     /* ... right-hand terms without them */
-        for (uint32_t t = 0; t < qs[i].n_terms; ++t) {
-            uint32_t id = qs[i].terms[t].term_id;
-            /* the candidates are the conjunction of the REQUIRED terms; right-hand terms (excluded / optional) are only probed */
-            const bool required = qs[i].op == XGM_OP_OR || ((qs[i].req_mask >> t) & 1u);
-            if (id == UINT32_MAX) { if (required) { min_df = 0; all_dense = false; } continue; }
-            const double df = idx->term_df[id];
-            const bool dense = bp->andw && !bp->wide && (!bp->phrase || idx->view.dense_pos) && idx->dense_min_df && (uint64_t)idx->term_df[id] >= idx->dense_min_df;
-            if (!dense) { sparse_blocks += (required ? 1.0 : 0.25) * (df / XGM_BLOCK + std::min<double>(df, n_stripes)); if (required) all_dense = false; }
-            if (!dense) { if (required) ++sparse_req; else sparse_rhs = true; }
-            if (!required) continue;
-            min_df = std::min(min_df, df);
-            dens *= df / n_docs;
-        }
-        /* AND visits only stripes where the rarest term has postings */
-        const double stripes = qs[i].op == XGM_OP_OR ? n_stripes : std::min<double>(n_stripes, min_df);
-        const double cand_per_stripe = all_dense ? Wd * dens : (stripes > 0 ? min_df / stripes : 0.0);
-        conj_per_stripe[i] = cand_per_stripe;
-        /* a candidate of a positional query costs a 64-byte sector per term, its positions and the predicate on top of the probe */
-        static const double phrase_cand = getenv("XGM_PHRASE_CAND_COST") ? atof(getenv("XGM_PHRASE_CAND_COST")) : 0.25;
-        /* ... and with three or more terms the matches are rarer, the query-wide threshold comes later and more of the candidates are tested
-         * (C5's `t70 t11 t5`: 38 matches, 120 k tests: its 41 units ran as long as the whole launch) */
-        static const double phrase_t3 = getenv("XGM_PHRASE_T3_COST") ? atof(getenv("XGM_PHRASE_T3_COST")) : 2.0;      /* A/B switch; measured C5 231 / 253 / 248 k queries/s at 1 / 2 / 4 */
-        const double per_cand = bp->phrase ? phrase_cand * (qs[i].n_terms >= 3 ? phrase_t3 : 1.0) : 0.03;
-        cost[i] = stripes * (bp->andw ? 15.0 : 8.0) + 0.9 * sparse_blocks + per_cand * cand_per_stripe * qs[i].n_terms * stripes + 1.0;
-        if (bp->andw && !bp->phrase && min_df > 0 && sparse_req <= 1 && !sparse_rhs && qs[i].n_terms <= 8) {
-            /* the conjunction kernel's queue path (measured per unit on MI355X, tools/units.py, in ~1k cycles of a wave
-             * at 4 waves per SIMD): the producer costs ~8 per stripe when the candidates are the AND of the bitmaps and
-             * ~0.05 per posting when they are the rarest term's postings; a probed candidate ~0.11, a weighed match
-             * ~0.15 (more with optional terms to sum) */
-            const double cands = sparse_req ? min_df : Wd * dens * n_stripes;
-            const double matches = sparse_req ? min_df * dens / std::max(1e-12, min_df / n_docs) : cands;
-            cost[i] = (sparse_req ? 4.0 + 0.3 * stripes : 8.0 * stripes) + 0.16 * cands + (bp->sided == 2 ? 0.22 : 0.15) * matches + 1.0;
-        } else if (bp->andw && !bp->phrase) {
-            cost[i] = stripes * 28.0 + 0.9 * sparse_blocks + per_cand * cand_per_stripe * qs[i].n_terms * stripes + 1.0;
-        }
-        if (dq[i].flags & XGM_QF_FLAT) {
-            /* xgm_flat_unit: rounds of 64 postings of the lead term, whatever stripes they fall in (~3 k cycles a round: two dependent gathers;
-             * a binary search per other term that has no containers) + the unit's prologue.  (Fitted before the body probed in two stages:
-             * a round that nobody survives now ends after the first gather — the constants await a re-fit from unit headers) */
-            double flat_others = 0;
-            for (uint32_t t = 1; t < qs[i].n_terms; ++t) {
-                const uint32_t id = qs[i].terms[t].term_id;
-                if (id != UINT32_MAX && !(idx->view.n_dense && (uint64_t)idx->term_df[id] >= idx->dense_min_df)) flat_others += 1.0;
-            }
-            cost[i] = 2.0 + (double)idx->term_df[qs[i].terms[0].term_id] / 64.0 * (3.0 + 2.0 * flat_others);
-        }
-        if (bp->orw) {
-            /* every stripe: the terms' bitmaps / block decodes (twice where candidates remain) and a
-             * share of the union that survives the MaxScore pruning */
-            double sum_df = 0, blocks = 0;
-            for (uint32_t t = 0; t < qs[i].n_terms; ++t) {
-                uint32_t id = qs[i].terms[t].term_id;
-                if (id == UINT32_MAX) continue;
-                const double df = idx->term_df[id];
-                sum_df += df;
-                if (bp->wide || (uint64_t)idx->term_df[id] < idx->dense_min_df || idx->dense_min_df == 0) blocks += df / XGM_BLOCK + std::min<double>(df, n_stripes);
-            }
-            /* (the documents weighed are a small share of the union since the threshold starts at the planner's guess) */
-            cost[i] = n_stripes * (10.0 + 3.0 * qs[i].n_terms) + 1.8 * blocks + 0.001 * sum_df + 1.0;
-        }
-        total_cost += cost[i];
-    }
-    /* units per launch: ~3 per wave slot of the chip (4 waves per SIMD for the conjunction kernel; the disjunction kernel runs 2 and
-     * pays a longer prologue per unit) */
-    static const double orw_units = getenv("XGM_ORW_UNITS") ? atof(getenv("XGM_ORW_UNITS")) : 8192.0;      /* A/B switch for measurements */
-    static const double and_units = getenv("XGM_TARGET_UNITS") ? atof(getenv("XGM_TARGET_UNITS")) : 12288.0;      /* A/B switch for measurements */
-    /* a SMALL batch (a server's natural batches are a few dozen queries, xgm_index_set_batching) keeps the units-per-query ratio of a
-     * full one instead of the full unit count: a 24-query batch cut into 12 288 units spends more on its work list (196 KB built, staged,
-     * uploaded) and on scheduling 3 072 tiny workgroups than on matching.  XGM_UNITS_PER_QUERY: A/B switch (0 = rounds 1-3). */
-    static const double units_per_query = getenv("XGM_UNITS_PER_QUERY") ? atof(getenv("XGM_UNITS_PER_QUERY")) : 48.0;
-    static const double units_floor = getenv("XGM_UNITS_FLOOR") ? atof(getenv("XGM_UNITS_FLOOR")) : 3072.0;                     /* A/B switch */
-    const double scaled_units = (units_per_query > 0.0 && nq > 4u) ? std::min(and_units, std::max(units_floor, units_per_query * (double)nq)) : and_units;
-    /* ... and a disjunction launch of a FEW queries (the class split leaves xgm_orw_kernel the odd query xgm_orw2_kernel does not take) is not cut
-     * into 8 192 units of one stripe each: 32 units per query, at least 1 024 */
-    const double orw_scaled = nq >= 192u ? orw_units : std::min(orw_units, std::max(1024.0, 32.0 * (double)nq));
-    const double target_units = bp->orw ? orw_scaled : scaled_units;
-    double unit_cost = std::max(1.0, total_cost / (wave_units ? target_units : 3072.0));
-    if (wave_units) {
-        /* the floor of g_min units per query (the LDS table bounds a unit's stripes) eats part of the budget: raise the
-         * unit cost until the batch fits ~12288 units again (3 per wave slot of the chip) */
-        for (int it = 0; it < 8; ++it) {
-            double units = 0;
-            for (uint32_t i = 0; i < nq; ++i) units += std::min<double>(g_max, std::max<double>(g_min, std::ceil(cost[i] / unit_cost)));
-            if (units <= target_units * 1.03) break;
-            unit_cost *= std::max(1.02, units / target_units);
-        }
-    }
-    bp->work.clear();
-    uint32_t spg_used = 1;
-    /* units in descending cost order (longest first); the units of a query share one cost, so ordering the QUERIES
-     * (stable) orders the units exactly as a stable sort of all of them would */
-    std::vector<uint32_t> gqv(nq), spgv(nq), order(nq), subv(nq, 1u);       /* subv: LIST — units per stripe (1, 2 or 4: parts of a stripe, see xgm_dense_unit) */
-    uint32_t g_most_q = 0;
-    /* positional queries: what a unit costs depends on how soon it holds k matches (until then every candidate's positions are tested),
-     * which the cost model cannot know — a 3-term phrase of frequent terms with few matches ran 2 ms in ONE 30-stripe unit while the
-     * rest of the launch took 0.6 ms (tools/qcost.py, round 4, BEFORE the dense body tested survivors from LDS-staged positions).  A/B switch:
-     * XGM_PHRASE_UNIT_STRIPES = n bounds a unit of such a query to n stripes (0 = off, the default). */
-    static const uint32_t phrase_unit_stripes = getenv("XGM_PHRASE_UNIT_STRIPES") ? (uint32_t)atoi(getenv("XGM_PHRASE_UNIT_STRIPES")) : 0u;   /* (measured with the LDS-staged positional test in place: C5 113.3 k queries/s unbounded, 109.5 k at 8 stripes, 100.9 k at 4: off) */
-    for (uint32_t i = 0; i < nq; ++i) {
-        uint32_t gq = (uint32_t)std::min<double>(g_max, std::max<double>(g_min, std::ceil(cost[i] / unit_cost)));
-        if (bp->phrase && bp->andw && phrase_unit_stripes && (dq[i].flags & XGM_QF_DENSE) && nq > 4u)
-            gq = std::max(gq, std::min(g_max, (n_stripes + phrase_unit_stripes - 1u) / phrase_unit_stripes));
-        if (list && bp->phrase && (dq[i].flags & XGM_QF_DENSE)) {
-            /* a LIST unit tests the positions of EVERY document of the conjunction in its range, in docid order, until the query's first matches are
-             * found: the launch ends with the longest such walk (measured, round 6: a 3-stripe unit of `t3 t8 t9` — 7 000 documents of the conjunction,
-             * 104 matches in the shard — ran 2.5 M cycles, the whole launch 1.27 ms).  Units of about XGM_LIST_UNIT_DOCS documents: the later ones
-             * cost nothing once the earlier ones hold the matches that decide the page (PrefixList::look_back) */
-            static const double list_unit_docs = getenv("XGM_LIST_UNIT_DOCS") ? atof(getenv("XGM_LIST_UNIT_DOCS")) : 1024.0;      /* A/B switch */
-            const uint32_t spg_l = (uint32_t)std::max(1.0, std::min(32.0, std::floor(list_unit_docs / std::max(1.0, conj_per_stripe[i]))));
-            gq = std::max(gq, std::min(n_stripes, (n_stripes + spg_l - 1u) / spg_l));
-            /* ... and below one stripe: halves or quarters of it (word-major bitmaps: a component of the lanes' words is a quarter of the stripe) */
-            static const bool no_parts = getenv("XGM_LIST_NO_STRIPE_PARTS") != nullptr;      /* A/B switch */
-            if (!no_parts && xgm_dense_word_major() && idx->hdr.stripe_bits >= 9u && conj_per_stripe[i] > 1.5 * list_unit_docs && (uint64_t)n_stripes * 4u < (1u << 24))
-                subv[i] = conj_per_stripe[i] > 3.0 * list_unit_docs ? 4u : 2u;
-        }
-        uint32_t spg = (n_stripes + gq - 1) / gq;
-        gq = (n_stripes + spg - 1) / spg;
-        if (subv[i] > 1u && spg == 1u) gq = n_stripes * subv[i]; else subv[i] = 1u;
-        spg_used = std::max(spg_used, spg);
-        gqv[i] = gq; spgv[i] = spg; order[i] = i;
-        g_most_q = std::max(g_most_q, gq);
-    }
-    /* parts: units [p * upp, (p + 1) * upp) of query q are pseudo-query p * nq + q of goff */
-    /* xgm_andw_kernel merges a query's lists in its last unit, whatever their number (XGM_NO_FUSED_MERGE: A/B switch, the variant tests) */
-    static const bool no_fused = getenv("XGM_NO_FUSED_MERGE") != nullptr;
-    /* ... xgm_orw_kernel can as well (round 6) — OPT-IN, XGM_OR_FUSED_MERGE=1: measured on the MI355X it LOSES (C3: 135.1 k queries/s, kernel 1.848 ms, against
-     * 139.1 k / 1.774 ms with the merge launch): one wave merging 32 lists of 100 candidates lengthens the launch's tail by more than the merge launch and the
-     * gap before it cost; the conjunction's k = 10 lists are another matter */
-    static const bool or_fused = getenv("XGM_OR_FUSED_MERGE") != nullptr;
-    bp->fused = ((bp->andw && !no_fused) || (bp->orw && !bp->orw2 && !no_fused && or_fused)) && mode == 0;                                                    /* (the stand-alone dense kernel, XGM_DENSE_KERNEL=1, finishes its queries the same way) */
-    /* (list: xgm_andw_list_kernel's units are walked in stripe order by xgm_frozen_finish_kernel, whatever their number: one part) */
-    const uint32_t P = (bp->fused || mode != 0) ? 1u : (g_most_q + units_per_part - 1) / units_per_part;
-    bp->parts = std::max(1u, P);
-    const uint32_t upp = bp->parts > 1 ? units_per_part : g_most_q + 1u;
-    bp->goff.assign((size_t)nq * bp->parts + 1, 0);
-    for (uint32_t p = 0; p < bp->parts; ++p)
-        for (uint32_t i = 0; i < nq; ++i) {
-            const uint32_t lo = std::min(gqv[i], p * upp), hi = std::min(gqv[i], (p + 1) * upp);
-            bp->goff[(size_t)p * nq + i + 1] = bp->goff[(size_t)p * nq + i] + (bp->parts > 1 ? hi - lo : gqv[i]);
-        }
-    /* (round 6, measured and dropped: the units of queries that take the same body of xgm_andw_kernel — dense / flat / queue — next to each other in the
-     *  grid, for the instruction cache: 0.3404 vs 0.3396 ms per launch of C2, no difference) */
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return cost[a] / gqv[a] > cost[b] / gqv[b]; });
-    bp->work.reserve(bp->goff.back());
-    for (uint32_t oi = 0; oi < nq; ++oi) {
-        const uint32_t i = order[oi], gq = gqv[i], spg = spgv[i];
-        for (uint32_t g = 0; g < gq; ++g) {
-            xgm_work w;
-            const uint32_t p = bp->parts > 1 ? g / upp : 0u;
-            w.qi = i; w.s_begin = g * spg; w.s_end = std::min(n_stripes, (g + 1) * spg); w.slot = bp->goff[(size_t)p * nq + i] + (g - p * (bp->parts > 1 ? upp : 0u));
-            if (subv[i] > 1u) {                                    /* part g % sub of stripe g / sub: its component mask rides in s_end's top byte */
-                const uint32_t sub = subv[i], st = g / sub, part = g % sub;
-                w.s_begin = st; w.s_end = (st + 1u) | ((sub == 4u ? (1u << part) : (3u << (2u * part))) << 24);
-            }
-            bp->work.push_back(w);
-        }
-    }
-    /* a LIST launch: stripe order — the units of lower stripes are done (and have published their match counts) when those of higher stripes
-     * start, which then have nothing to do for every query whose page is decided (PrefixList::look_back) */
-    static const bool list_lpt = getenv("XGM_LIST_LPT_ORDER") != nullptr;            /* A/B switch: heaviest first, as the other launches */
-    if (list && !list_lpt) {
-        /* (a counting sort on the first stripe, stable: tens of thousands of units per batch — a comparison sort of them was the host's largest item) */
-        static thread_local std::vector<uint32_t> at;
-        static thread_local std::vector<xgm_work> sorted;
-        at.assign((size_t)n_stripes + 1u, 0u);
-        for (const xgm_work& w : bp->work) ++at[w.s_begin + 1u];
-        for (uint32_t st = 0; st < n_stripes; ++st) at[st + 1u] += at[st];
-        sorted.resize(bp->work.size());
-        for (const xgm_work& w : bp->work) sorted[at[w.s_begin]++] = w;
-        bp->work.swap(sorted);
-    }
-    bp->n_work = (uint32_t)bp->work.size();
-    bp->stripes_per_group = spg_used;
-    uint32_t g_most = 0;
-    for (size_t i = 0; i + 1 < bp->goff.size(); ++i) g_most = std::max(g_most, bp->goff[i + 1] - bp->goff[i]);
-    const size_t smem = bp->andw ? xgm_andw_smem_bytes(idx->hdr.stripe_bits, bp->tab_terms, bp->cap, bp->wide, bp->stripes_per_group, bp->phrase, bp->sided == 2)
-                        : bp->orw2 ? xgm_orw2_smem_bytes(idx->hdr.stripe_bits, bp->tab_terms, bp->cap, bp->stripes_per_group, bp->orw2 == 2)
-                        : bp->orw ? xgm_orw_smem_bytes(idx->hdr.stripe_bits, bp->tab_terms, bp->cap, bp->wide, bp->stripes_per_group)
-                                 : xgm_match_smem_bytes(idx->hdr.stripe_bits - bp->sub_bits, bp->tab_terms, bp->phrase, bp->cap, bp->wide, bp->stripes_per_group);
-    if (smem > 160u * 1024u) return XGM_UNSUPPORTED;
-    bp->merge_cap = std::max(512u, next_pow2(g_most * bp->k_max));     /* fixed window of k_max per unit */
-    bp->k_stride_c = bp->k_max;
-    return XGM_OK;
-}
-
-
-/* Runs one batch of ONE kernel class (or a batch whose mix plan_batch resolves by itself); results land in rows
+/* Runs one batch of ONE kernel class (or a batch whose mix xgm_plan_batch resolves by itself); results land in rows
  * rows[i] (i when rows == NULL) of d_hits / d_hdrs (device).  Asynchronous on `stream`. */
 constexpr int XGM_LIST_DECLINED = 2;       /* run_class_batch(list): the batch is not one xgm_andw_list_kernel takes — nothing was enqueued */
 static int run_class_batch(xgm_index* idx, XgmScratch* s, hipStream_t stream, const xgm_query* qs, uint32_t nq, uint32_t k_stride,
@@ -1048,11 +548,11 @@ static int run_class_batch(xgm_index* idx, XgmScratch* s, hipStream_t stream, co
     xgm_dev_query* h_dq = (xgm_dev_query*)plan_buf.data();
     double* h_mp = (double*)(h_dq + nq);
     uint32_t* h_kq = (uint32_t*)(h_mp + nq);
-    static thread_local BatchPlan bp_tls;
-    BatchPlan& bp = bp_tls;
+    static thread_local XgmBatchPlan bp_tls;
+    XgmBatchPlan& bp = bp_tls;
     bp.reset();
     const uint64_t t_pb = now_ns();
-    if ((rc = plan_batch(idx, qs, nq, h_dq, h_kq, h_mp, &bp, false, mode))) return rc;
+    if ((rc = xgm_plan_batch(idx, qs, nq, h_dq, h_kq, h_mp, &bp, false, mode))) return rc;
     const uint64_t t_st = now_ns();
     g_host_ns[1] += t_st - t_pb;
     if (k_stride < bp.k_max) return xgm_set_error(XGM_E_INVALID, "k_stride %u < first+maxitems %u", k_stride, bp.k_max);
@@ -1082,7 +582,7 @@ static int run_class_batch(xgm_index* idx, XgmScratch* s, hipStream_t stream, co
     if ((rc = grow(&s->d_cand, &s->cap_cand, (size_t)bp.n_work * bp.k_stride_c))) return rc;
     if ((rc = grow(&s->d_ghdr, &s->cap_ghdr, (size_t)bp.n_work))) return rc;
     /* every per-call input goes up in ONE copy: [dev queries | max_possible | work list | k | group offsets] */
-    const uint32_t P = bp.parts, npq = nq * P;              /* pseudo-queries of the units' merge (parts of queries, plan_batch) */
+    const uint32_t P = bp.parts, npq = nq * P;              /* pseudo-queries of the units' merge (parts of queries, xgm_plan_batch) */
     const size_t o_dq = 0, b_dq = (size_t)nq * sizeof(xgm_dev_query);
     const size_t o_mp = o_dq + b_dq, b_mp = (size_t)npq * 8;
     const size_t o_wk = o_mp + b_mp, b_wk = (size_t)bp.n_work * sizeof(xgm_work);
@@ -1101,7 +601,7 @@ static int run_class_batch(xgm_index* idx, XgmScratch* s, hipStream_t stream, co
     if (rows) memcpy(hin + o_ro, rows, b_ro);
     /* every query of the batch a conjunction over probe containers only (dense_kind, all of one kind): the kernel written for that */
     bool dense = mode == 0 && bp.andw && !bp.wide && bp.sided == 0 && bp.stripes_per_group <= xgm_dense_max_stripes();
-    for (uint32_t i = 0; i < nq && dense; ++i) dense = dense_kind(idx, qs[i]) == (bp.phrase ? 2 : 1);
+    for (uint32_t i = 0; i < nq && dense; ++i) dense = xgm_dense_kind(idx, qs[i]) == (bp.phrase ? 2 : 1);
     static const bool dense_class_old_kernel = getenv("XGM_DENSE_CLASS_OLD_KERNEL") != nullptr;      /* A/B: the same class split, xgm_andw_kernel for both */
     if (dense_class_old_kernel) dense = false;
     const bool fused = bp.fused;
@@ -1173,7 +673,7 @@ static int run_class_batch(xgm_index* idx, XgmScratch* s, hipStream_t stream, co
     L.cand = s->d_cand; L.ghdr = s->d_ghdr;
     hipEvent_t pe0 = nullptr, pe1 = nullptr;
     if ((rc = next_event_pair(idx, &pe0, &pe1))) return rc;
-    idx->last_kernel = all ? "xgm_andw_all_kernel" : list ? "xgm_andw_list_kernel" : dense ? "xgm_dense_kernel" : bp.andw ? "xgm_andw_kernel" : bp.orw2 ? "xgm_orw2_kernel" : bp.orw ? "xgm_orw_kernel" : bp.and_only ? "xgm_and_kernel" : "xgm_match_kernel";
+    idx->last_kernel = xgm_plan_kernel_name(bp, mode, dense).name;
     idx->last_ghdr = s->d_ghdr; idx->last_n_work = bp.n_work;        /* xgm_last_batch_traffic */
     idx->last_tallied = idx->tally;                                  /* (the slots below describe this batch, or no batch at all) */
     if (idx->tally) {                                                /* xgm_last_batch_bitmap_skipped: which headers belong to plain dense units */
@@ -1234,7 +734,7 @@ static int run_class_batch(xgm_index* idx, XgmScratch* s, hipStream_t stream, co
         if ((rc = xgm_launch_merge(s->d_cand, s->d_ghdr, s->d_goff, bp.k_stride_c, s->d_kq, npq, bp.merge_cap, k_stride, s->d_part_hits,
                                    s->d_part_hdrs, s->d_maxposs, nullptr, stream)))
             return rc;
-        if ((rc = xgm_launch_merge_parts(s->d_part_hits, s->d_part_hdrs, P, nq, k_stride, s->d_kq, std::max(256u, next_pow2(P * k_stride)), d_hits, d_hdrs,
+        if ((rc = xgm_launch_merge_parts(s->d_part_hits, s->d_part_hdrs, P, nq, k_stride, s->d_kq, std::max(256u, xgm_next_pow2(P * k_stride)), d_hits, d_hdrs,
                                          d_rows, stream)))
             return rc;
     }
@@ -1251,120 +751,8 @@ extern "C" int xgm_debug_host_ns(uint64_t* out4) {      /* (u64[8]) */
     return XGM_OK;
 }
 
-/* Kernel class of a planned query: which match kernel serves it best.  A server's natural batch is heterogeneous
- * (Xapiand's HTTP threads issue whatever the clients send): run_batch cuts it into one launch per class present instead
- * of sending the whole batch to the slowest common denominator. */
-enum { XGM_CLS_AND = 0, XGM_CLS_SIDED1, XGM_CLS_SIDED2, XGM_CLS_PHRASE, XGM_CLS_OR, XGM_CLS_OTHER, XGM_CLS_BIGK, XGM_CLS_DENSE_AND, XGM_CLS_DENSE_PHRASE,
-       XGM_CLS_OR2,                              /* disjunctions for xgm_orw2_kernel (or2_kind): ONE launch — its flat-array instantiation takes the queries whose
-                                                    every term has a container too (measured, round 5: a launch per kind cost 3.7 ms per 256-query batch against
-                                                    2.0 for the old kernel alone: three tails, three sets of unit prologues) */
-       XGM_CLS_COUNTED,                          /* plain conjunctions with XGM_REPLAY_BATCH_COUNT that xgm_andw_all_kernel takes: ProtoMSet's count on the device */
-       XGM_CLS_FROZEN,                           /* positional queries answered as the reference answers them (XGM_REPLAY_BATCH_FROZEN) that xgm_andw_list_kernel takes */
-       XGM_CLS_COUNT };
-
-/* xgm_dense_kernel's queries (xgm_dense_and.hip): a conjunction / FILTER — or a positional query that prunes by weight — of 2 to 4
- * terms that ALL have probe containers (xgm_build_dense's own criterion), a page of at most 64.  1 = plain, 2 = positional, 0 = no. */
-static int dense_kind(const xgm_index* idx, const xgm_query& q, bool fused) {
-    /* (fused: the question xgm_andw_kernel's own dense body asks — the same shapes, plain only, decided per query inside one launch)
-     * OFF by default (round 3 measurements): as a launch of its own the kernel costs more than it gains — the class split
-     * means two match + merge launches per batch.  XGM_DENSE_KERNEL=1 switches it on (A/B runs, tests/test_gpu_variants.py). */
-    static const bool off_alone = getenv("XGM_DENSE_KERNEL") == nullptr || getenv("XGM_NO_ANDW") != nullptr || getenv("XGM_NO_AND_KERNEL") != nullptr;
-    static const bool off_fused = getenv("XGM_NO_DENSE_BODY") != nullptr;                           /* A/B switch for measurements */
-    const bool off = fused ? off_fused : off_alone;
-    static const bool no_pos_prune = getenv("XGM_NO_POS_PRUNE") != nullptr;
-    static const bool no_phrase_w = getenv("XGM_NO_PHRASEW") != nullptr;
-    if (off || idx->view.n_dense == 0 || idx->dense_min_df == 0 || idx->hdr.stripe_bits > 13u) return 0;
-    const uint32_t T = q.n_terms, k = q.first + q.maxitems;
-    if (T < 2u || T > xgm_dense_max_terms() || k == 0u || k > xgm_dense_max_k()) return 0;
-    const bool positional = (q.op == XGM_OP_PHRASE || q.op == XGM_OP_NEAR) && q.phrase_active;
-    if (!(q.op == XGM_OP_AND || q.op == XGM_OP_FILTER || positional)) return 0;
-    if (positional && (no_pos_prune || no_phrase_w || !idx->view.dense_pos || q.check_at_least > k)) return 0;
-    if ((q.op == XGM_OP_PHRASE || q.op == XGM_OP_NEAR) && !positional) return 0;
-    for (uint32_t t = 0; t < T; ++t) {
-        const uint32_t id = q.terms[t].term_id;
-        if (id == UINT32_MAX || (uint64_t)idx->term_df[id] < idx->dense_min_df || idx->term_wdfub[id] > 254u) return 0;
-    }
-    return positional ? 2 : 1;
-}
-
-/* xgm_flat_unit's queries (xgm_flat_body.inc): a plain conjunction / FILTER of 2..4 terms, a page of at most 64, whose FIRST plan term — the
- * rarest: MultiAndPostList order — has no probe containers but a flat posting array, every other term containers or a flat array.  The
- * criteria are xgm_build_dense's own (xgm_dense.hip: build_containers / build_flat). */
-static bool flat_kind(const xgm_index* idx, const xgm_query& q) {
-    static const bool off = getenv("XGM_NO_FLAT") != nullptr || getenv("XGM_NO_DENSE") != nullptr || getenv("XGM_NO_ANDW") != nullptr ||
-                            getenv("XGM_NO_AND_KERNEL") != nullptr;
-    if (off || !idx->view.flat_off || idx->hdr.stripe_bits > 13u) return false;
-    const uint32_t T = q.n_terms, k = q.first + q.maxitems;
-    if (T < 2u || T > xgm_dense_max_terms() || k == 0u || k > xgm_dense_max_k()) return false;
-    const bool positional = (q.op == XGM_OP_PHRASE || q.op == XGM_OP_NEAR) && q.phrase_active;
-    if (!(q.op == XGM_OP_AND || q.op == XGM_OP_FILTER || positional)) return false;
-    /* positional: the flat arrays carry position offsets, the containers position bases; only queries that prune by weight (XGM_QF_POSPRUNE) */
-    static const bool no_pos_prune = getenv("XGM_NO_POS_PRUNE") != nullptr, no_phrase_w = getenv("XGM_NO_PHRASEW") != nullptr,
-                      no_flat_phrase = getenv("XGM_NO_FLAT_PHRASE") != nullptr;
-    if (positional && (no_pos_prune || no_phrase_w || no_flat_phrase || !idx->view.flat_pos || q.check_at_least > k)) return false;
-    for (uint32_t t = 0; t < T; ++t) {
-        const uint32_t id = q.terms[t].term_id;
-        if (id == UINT32_MAX || idx->term_wdfub[id] > 254u || idx->term_df[id] == 0u) return false;
-        const bool dense = idx->view.n_dense && (uint64_t)idx->term_df[id] >= idx->dense_min_df;
-        if (t == 0u && dense) return false;
-        if (positional && dense && !idx->view.dense_pos) return false;
-    }
-    return true;
-}
-
-/* A disjunction xgm_orw2_kernel takes (xgm_or.hip): <= 8 terms, first + maxitems <= 192, every term of the shard with a one-byte wdf and either a
- * probe container (→ 1 when all have one) or a flat posting array (→ 2; at most two such terms per query).  0: xgm_orw_kernel. */
-static int or2_kind(const xgm_index* idx, const xgm_query& q) {
-    if (q.op != XGM_OP_OR || q.n_terms == 0 || q.n_terms > 8u || (uint64_t)q.first + q.maxitems > 192u || !xgm_orw2_enabled()) return 0;
-    if (!idx->view.n_dense || !idx->dense_min_df) return 0;
-    uint32_t flat = 0;
-    for (uint32_t t = 0; t < q.n_terms; ++t) {
-        const uint32_t id = q.terms[t].term_id;
-        if (id == UINT32_MAX) continue;
-        if (idx->term_wdfub[id] > 254u) return 0;
-        if ((uint64_t)idx->term_df[id] >= idx->dense_min_df) continue;
-        if (!idx->view.flat_off || idx->flat_postings >= 0xFFFFFFFFull) return 0;
-        if (++flat > 2u) return 0;
-    }
-    return flat ? 2 : 1;
-}
-
-static int classify_query(const xgm_index* idx, const xgm_query& q) {
-    const uint32_t T = q.n_terms;
-    if (const int dk = dense_kind(idx, q)) return dk == 2 ? XGM_CLS_DENSE_PHRASE : XGM_CLS_DENSE_AND;
-    /* the wave kernels keep first + maxitems <= 192 candidates per unit: deeper pages go together to the workgroup kernels
-     * instead of dragging a whole class there */
-    if (q.op != XGM_OP_OR && q.first + q.maxitems > 192u) return XGM_CLS_BIGK;
-    const uint32_t prefix = q.req_mask && !(q.req_mask & (q.req_mask + 1u));            /* required terms = plan positions [0, n_req) */
-    switch (q.op) {
-    case XGM_OP_OR: return or2_kind(idx, q) ? XGM_CLS_OR2 : XGM_CLS_OR;
-    case XGM_OP_PHRASE:
-    case XGM_OP_NEAR: return (q.phrase_active && T >= 2u) ? XGM_CLS_PHRASE : XGM_CLS_OTHER;
-    case XGM_OP_AND:
-    case XGM_OP_FILTER: return T >= 2u ? XGM_CLS_AND : XGM_CLS_OTHER;
-    case XGM_OP_AND_NOT: return (T >= 2u && T <= 8u && prefix && (q.req_mask | q.neg_mask) == (1u << T) - 1u) ? XGM_CLS_SIDED1 : XGM_CLS_OTHER;
-    case XGM_OP_AND_MAYBE: return (T >= 2u && T <= 8u && prefix) ? XGM_CLS_SIDED2 : XGM_CLS_OTHER;
-    default: return XGM_CLS_OTHER;
-    }
-}
-
 static std::atomic<uint64_t> g_batch_replays[3];    /* diagnostics: rows listed on the device / declined there / answered by xgm_search_replay when collected */
 extern "C" int xgm_debug_batch_replay_info(uint64_t* out3) { if (!out3) return -1; for (int i = 0; i < 3; ++i) out3[i] = g_batch_replays[i].load(); return 0; }
-
-/* xgm_andw_list_kernel's queries: positional, a page of at most 64 with check_at_least inside it, 2..4 terms that all have probe containers — or are
- * led by a long-tail term with a flat posting array (the criteria of the two bodies that have a LIST form) */
-static bool list_kind(const xgm_index* idx, const xgm_query& q) {
-    const bool positional = (q.op == XGM_OP_PHRASE || q.op == XGM_OP_NEAR) && q.phrase_active;
-    return positional && (dense_kind(idx, q, true) == 2 || flat_kind(idx, q));
-}
-
-/* xgm_andw_all_kernel's queries: a plain conjunction / FILTER the dense or the flat body takes, a page of at most 64 with check_at_least inside it */
-static bool all_kind(const xgm_index* idx, const xgm_query& q) {
-    if (q.op != XGM_OP_AND && q.op != XGM_OP_FILTER) return false;
-    const uint32_t k = q.first + q.maxitems;
-    if (k == 0u || k > 64u || q.check_at_least > k) return false;
-    return dense_kind(idx, q, true) == 1 || flat_kind(idx, q);
-}
 
 /* Runs the batch; results land in d_hits / d_hdrs (device).  Asynchronous on `stream`.
  * d_extra != NULL (device, [nq] zeroed): the queries' XGM_REPLAY_BATCH_* bits are honoured — rows the device answers get their extra word
@@ -1379,14 +767,14 @@ static int run_batch(xgm_index* idx, XgmScratch* s, hipStream_t stream, const xg
     uint32_t present = 0;
     s->last_stop = nullptr;
     for (uint32_t i = 0; i < nq; ++i) {
-        cls[i] = (uint8_t)classify_query(idx, qs[i]);
+        cls[i] = (uint8_t)xgm_classify_query(idx, qs[i]);
         const uint32_t rp = (d_extra && host_replay) ? qs[i].replay : 0u;
         if ((rp & XGM_REPLAY_BATCH_FROZEN) && (qs[i].op == XGM_OP_PHRASE || qs[i].op == XGM_OP_NEAR) && qs[i].phrase_active) {
-            if (!no_list && !no_split && list_kind(idx, qs[i])) { cls[i] = XGM_CLS_FROZEN; ++g_batch_replays[0]; }
+            if (!no_list && !no_split && xgm_list_kind(idx, qs[i])) { cls[i] = XGM_CLS_FROZEN; ++g_batch_replays[0]; }
             else host_replay->push_back(i);
         } else if (rp & XGM_REPLAY_BATCH_COUNT) {
             /* ProtoMSet's count: conjunctions on the device (xgm_andw_all_kernel + xgm_count.hip), any other operator by xgm_search_replay when the batch is collected */
-            if (!no_list && !no_split && all_kind(idx, qs[i])) { cls[i] = XGM_CLS_COUNTED; ++g_batch_replays[0]; }
+            if (!no_list && !no_split && xgm_all_kind(idx, qs[i])) { cls[i] = XGM_CLS_COUNTED; ++g_batch_replays[0]; }
             else host_replay->push_back(i);
         }
         if (count[cls[i]]++ == 0) ++present;
@@ -1628,7 +1016,7 @@ static int search_batch_now(xgm_index* idx, const xgm_query* qs, uint32_t nq, ui
 
 /* ---- searches under a value sort (first version) -------------------------------------------------------------
  * One query at a time, synchronous, its own device buffers: correctness first.  Every query shape the workgroup kernel handles
- * (plain operators, PHRASE / NEAR, nested trees).  The unit decomposition is that kernel's (plan_batch with the wave kernels
+ * (plain operators, PHRASE / NEAR, nested trees).  The unit decomposition is that kernel's (xgm_plan_batch with the wave kernels
  * switched off); the units' candidates come back to the host, which merges them
  * under the same comparison the kernel ranks by. */
 
@@ -1819,17 +1207,17 @@ static int find_spy_column(xgm_index* idx, uint32_t slot, const uint32_t* counts
 /* ---- the host side of xgm_match_sorted_kernel, shared by every sorted, spied, collapsed and filtered search and by search_all_device --------
  * plan_sorted: the workgroup kernel's decomposition of the queries and what the sorted kernel declines.  k_limit: a caller's rows hold that many
  * hits per query (a page beyond them is the caller's error); UINT32_MAX where there is no such bound. */
-static int plan_sorted(xgm_index* idx, const xgm_query* qs, uint32_t nq, uint32_t k_limit, xgm_dev_query* dq, BatchPlan* bp) {
+static int plan_sorted(xgm_index* idx, const xgm_query* qs, uint32_t nq, uint32_t k_limit, xgm_dev_query* dq, XgmBatchPlan* bp) {
     std::vector<uint32_t> kq(nq);
     std::vector<double> mp(nq);
-    int rc = plan_batch(idx, qs, nq, dq, kq.data(), mp.data(), bp, true);
+    int rc = xgm_plan_batch(idx, qs, nq, dq, kq.data(), mp.data(), bp, true);
     if (rc) return rc;
     if (bp->andw || bp->orw || bp->and_only || bp->cap > 8u * XGM_WG) return XGM_UNSUPPORTED;
     for (uint32_t i = 0; i < nq; ++i) {
         if (dq[i].k == 0) return XGM_UNSUPPORTED;
         if (dq[i].k > k_limit) return xgm_set_error(XGM_E_INVALID, "k_stride %u < first + maxitems %u", k_limit, dq[i].k);
     }
-    if (xgm_match_sorted_smem_bytes(idx->hdr.stripe_bits - bp->sub_bits, bp->tab_terms, bp->phrase, bp->cap, bp->wide, bp->stripes_per_group) > 160u * 1024u) return XGM_UNSUPPORTED;
+    if (xgm_match_sorted_smem_bytes(idx->hdr.stripe_bits - bp->sub_bits, bp->tab_terms, bp->phrase, bp->cap, bp->wide, bp->stripes_per_group) > XGM_LDS_BUDGET) return XGM_UNSUPPORTED;
     return XGM_OK;
 }
 
@@ -1842,7 +1230,7 @@ struct SortedStage {
     uint32_t* d_counts = nullptr;            /* NULL without counters */
     xgm_match_launch L;
 };
-static int stage_sorted(xgm_index* idx, XgmScratch* sc, const xgm_dev_query* dq, uint32_t nq, const BatchPlan& bp, uint32_t kc, size_t count_bytes,
+static int stage_sorted(xgm_index* idx, XgmScratch* sc, const xgm_dev_query* dq, uint32_t nq, const XgmBatchPlan& bp, uint32_t kc, size_t count_bytes,
                         size_t pinned_extra, SortedStage* st) {
     int rc;
     const uint32_t n_work = bp.n_work;
@@ -1905,7 +1293,7 @@ struct SortedOpts {
 };
 
 /* nq searches under ONE sort (NULL: by relevance) in ONE launch: the workgroup kernel's units of every query go up in one work list
- * (plan_batch), every unit leaves its best k under the sort, the host merges each query's units.  A spy: the kernel counts every matching
+ * (xgm_plan_batch), every unit leaves its best k under the sort, the host merges each query's units.  A spy: the kernel counts every matching
  * document by its ordinal in the spy column, one row of counters per query.  A collapse key: the kernel collapses inside every unit, the
  * merge below once more per query; the matches per collapse key — the spy mechanism on the collapse column — give the items' collapse
  * counts and the collapsed lower bound. */
@@ -1941,7 +1329,7 @@ static int sorted_batch_core(xgm_index* idx, const xgm_query* qs, uint32_t nq, c
     int rc = use_device(idx->device);
     if (rc) return rc;
     std::vector<xgm_dev_query> dq(nq);
-    BatchPlan bp;
+    XgmBatchPlan bp;
     if ((rc = plan_sorted(idx, qs, nq, o.single ? UINT32_MAX : k_stride, dq.data(), &bp))) return rc;
     if (!o.single && bp.parts != 1u) return XGM_UNSUPPORTED;  /* (the batch entry points' own refusal; the merge below takes any number of parts) */
     if (o.single) k_stride = dq[0].k;
@@ -2715,7 +2103,7 @@ static int search_all_device(xgm_index* idx, const xgm_query* q, XgmScratch* sc,
     xgm_query q1 = *q;
     q1.first = 0; q1.maxitems = 1; q1.check_at_least = 0xFFFFFFFFu;          /* the kernel's own top-k is not used: keep it smallest; positions of every candidate tested */
     xgm_dev_query dq;
-    BatchPlan bp;
+    XgmBatchPlan bp;
     if ((rc = plan_sorted(idx, &q1, 1, UINT32_MAX, &dq, &bp))) return rc;
     dq.flags &= ~XGM_QF_POSPRUNE;
     if (list_conj && (dq.flags & XGM_QF_PHRASE)) dq.flags |= XGM_QF_LIST_CONJ;
@@ -3244,7 +2632,7 @@ static int merge_shards_device_on(xgm_index* idx, hipStream_t on, const void* d_
         uint32_t k_max = 1;
         for (uint32_t i = 0; i < nq; ++i) k_max = std::max(k_max, k[i]);
         if (k_max > k_stride) { rc = xgm_set_error(XGM_E_INVALID, "k > k_stride"); break; }
-        uint32_t cap = std::max(512u, next_pow2(n_shards * k_max));
+        uint32_t cap = std::max(512u, xgm_next_pow2(n_shards * k_max));
         if (cap > XGM_MERGE_CAP) { rc = XGM_UNSUPPORTED; break; }
         if ((rc = grow(&s->d_mkq, &s->cap_mkq, (size_t)nq))) break;
         if ((rc = grow_pinned(&s->h_up, &s->cap_up, (size_t)nq * 4))) break;
@@ -3689,7 +3077,7 @@ extern "C" int64_t xgm_debug_read_flat(xgm_index* idx, uint32_t term_id, uint32_
     if (!idx->d_flat_off || !idx->d_flat_did || !idx->d_flat_wdf) return 0;
     uint64_t o[2] = {0, 0};
     HIP_TRY(hipMemcpy(o, (const uint64_t*)idx->d_flat_off + term_id, 16, hipMemcpyDeviceToHost));
-    if (o[1] < o[0] || o[1] > idx->flat_postings) return xgm_set_error(XGM_E_INVALID, "flat slice of term %u out of range", term_id);
+    if (o[1] < o[0] || o[1] > idx->facts.flat_postings) return xgm_set_error(XGM_E_INVALID, "flat slice of term %u out of range", term_id);
     const uint64_t n = o[1] - o[0];
     if (n == 0) return 0;
     if (cap < n) return xgm_set_error(XGM_E_INVALID, "buffer too small");
@@ -3764,62 +3152,6 @@ int xgm_merge_cycles_fetch(unsigned long long* out8);
 extern "C" int xgm_debug_merge_cycles(unsigned long long* out8) { return xgm_merge_cycles_fetch(out8); }
 extern "C" int xgm_debug_orw_phase_cycles(unsigned long long* out8) { return xgm_orw_cycles_fetch(out8); }
 
-/* Diagnostics (host only — works on an XGM_DEVICE_NONE index): the decomposition a batch would be launched with.
- * kernel[32] receives the match kernel's name (and ":sided1" / ":sided2" / ":phrase" for the conjunction kernel's
- * instantiation); units receives (qi, s_begin, s_end, slot) per work unit in launch order; returns the number of
- * units (possibly > cap: only cap are written), or < 0 / XGM_UNSUPPORTED like a search would. */
-extern "C" int64_t xgm_debug_plan_batch(const xgm_index* idx, const xgm_query* qs, uint32_t nq, char* kernel, uint32_t* units, uint64_t cap) {
-    if (!idx || !qs || !kernel || (!units && cap)) return xgm_set_error(XGM_E_INVALID, "null argument");
-    if (nq == 0) return 0;
-    std::vector<xgm_dev_query> dq(nq);
-    std::vector<uint32_t> kq(nq);
-    std::vector<double> mp(nq);
-    BatchPlan bp;
-    int rc = plan_batch(idx, qs, nq, dq.data(), kq.data(), mp.data(), &bp);
-    if (rc) return rc;
-    snprintf(kernel, 32, "%s%s", bp.andw ? "xgm_andw_kernel" : bp.orw2 ? "xgm_orw2_kernel" : bp.orw ? "xgm_orw_kernel" : bp.and_only ? "xgm_and_kernel" : "xgm_match_kernel",
-             bp.andw && bp.phrase ? ":phrase" : bp.andw && bp.sided == 2 ? ":sided2" : bp.andw && bp.sided == 1 ? ":sided1" : "");
-    for (uint64_t i = 0; i < bp.work.size() && i < cap; ++i) {
-        units[4 * i] = bp.work[i].qi; units[4 * i + 1] = bp.work[i].s_begin; units[4 * i + 2] = bp.work[i].s_end; units[4 * i + 3] = bp.work[i].slot;
-    }
-    return (int64_t)bp.work.size();
-}
-
-/* Diagnostics (host only): the disjunction kernel's pruning inputs of one planned query — the guess of the final k-th weight and the
- * per-term weight bounds (largest wdf / wdf = 1), in plan order. */
-extern "C" int xgm_debug_or_bounds(const xgm_index* idx, const xgm_query* q, double* seed, double* ub, double* ub1) {
-    if (!idx || !q) return xgm_set_error(XGM_E_INVALID, "null argument");
-    xgm_dev_query d;
-    const int w = to_dev_query(idx, q, &d);
-    if (w <= 0) return XGM_UNSUPPORTED;
-    if (seed) *seed = d.theta_seed;
-    for (uint32_t t = 0; t < q->n_terms; ++t) { if (ub) ub[t] = d.ub[t]; if (ub1) ub1[t] = d.ub1[t]; }
-    return XGM_OK;
-}
-
-/* Diagnostics (host only): the launches a batch is cut into — one per kernel class present (run_batch) — as
- * "<kernel>[:variant]*<queries>" joined by ';' in launch order; returns the number of launches, or < 0 /
- * XGM_UNSUPPORTED like a search would. */
-extern "C" int xgm_debug_batch_launches(const xgm_index* idx, const xgm_query* qs, uint32_t nq, char* out, uint32_t cap) {
-    if (!idx || !qs || !out || cap == 0) return xgm_set_error(XGM_E_INVALID, "null argument");
-    out[0] = 0;
-    std::vector<std::vector<xgm_query>> by(XGM_CLS_COUNT);
-    for (uint32_t i = 0; i < nq; ++i) by[classify_query(idx, qs[i])].push_back(qs[i]);
-    int n = 0;
-    std::string acc;
-    for (auto& v : by) {
-        if (v.empty()) continue;
-        char name[32];
-        int64_t rc = xgm_debug_plan_batch(idx, v.data(), (uint32_t)v.size(), name, nullptr, 0);
-        if (rc < 0 || rc == XGM_UNSUPPORTED) return (int)rc;
-        if (n++) acc += ";";
-        acc += name;
-        acc += "*" + std::to_string(v.size());
-    }
-    snprintf(out, cap, "%s", acc.c_str());
-    return n;
-}
-
 /* Diagnostics: per work-unit (qi, s_begin, s_end, slot, t_start, t_end, matches, documents weighed)
  * of the LAST batch launched on this index from any thread; out is u64[8 * cap]; returns the number
  * of units. */
@@ -3842,3 +3174,9 @@ static int64_t debug_last_units(xgm_index* idx, unsigned long long* out, unsigne
     }
     return (int64_t)n;
 }
+
+#if defined(XGM_EMU) && !defined(XGM_EMU_PLANNER_UNIT)
+/* An emulation build (tests/emu) whose source list is older than xgm_batch_plan.cc still gets the planner: here.  tests/emu/Makefile lists the file
+ * and says so with -DXGM_EMU_PLANNER_UNIT. */
+#include "xgm_batch_plan.cc"
+#endif

@@ -201,7 +201,7 @@ static int build_narrow_doclen(xgm_index* idx) {
 static int build_flat(xgm_index* idx) {
     idx->view.flat_off = nullptr; idx->view.flat_did = nullptr; idx->view.flat_wdf = nullptr; idx->view.flat_pos = nullptr;
     for (void** p : {&idx->d_flat_off, &idx->d_flat_did, &idx->d_flat_wdf, &idx->d_flat_pos}) if (*p) { hipFree(*p); *p = nullptr; }
-    idx->flat_bytes = 0; idx->flat_postings = 0;
+    idx->flat_bytes = 0; idx->facts.flat_postings = 0; idx->facts.has_flat = false; idx->facts.flat_pos = false;
     /* XGM_NO_DENSE = no acceleration structures at all (the variant tests run the block decode K1 that way); XGM_NO_FLAT: this one off */
     if (getenv("XGM_NO_DENSE") || getenv("XGM_NO_FLAT")) return XGM_OK;
     const uint32_t T = idx->hdr.n_terms;
@@ -210,7 +210,7 @@ static int build_flat(xgm_index* idx) {
     uint64_t n = 0;
     for (uint32_t t = 0; t < T; ++t) {
         off[t] = n;
-        const bool dense = idx->view.n_dense && (uint64_t)idx->term_df[t] >= idx->dense_min_df && idx->term_wdfub[t] <= 254u;
+        const bool dense = idx->view.n_dense && (uint64_t)idx->term_df[t] >= idx->facts.dense_min_df && idx->term_wdfub[t] <= 254u;
         if (!dense && idx->term_df[t] && idx->term_wdfub[t] <= 254u) { n += idx->term_df[t]; terms.push_back(t); }
     }
     off[T] = n;
@@ -249,7 +249,7 @@ static int build_flat(xgm_index* idx) {
     idx->view.flat_did = (const uint32_t*)idx->d_flat_did;
     idx->view.flat_wdf = (const unsigned char*)idx->d_flat_wdf;
     idx->view.flat_pos = (const uint32_t*)idx->d_flat_pos;
-    idx->flat_postings = n;
+    idx->facts.has_flat = true; idx->facts.flat_pos = idx->d_flat_pos != nullptr; idx->facts.flat_postings = n;
     idx->flat_bytes = off.size() * 8 + n * (idx->d_flat_pos ? 9 : 5) + 768;
     idx->device_bytes += idx->flat_bytes;
     return XGM_OK;
@@ -271,6 +271,7 @@ static int build_containers(xgm_index* idx) {
     idx->view.dense_id = nullptr; idx->view.dense_dir = nullptr; idx->view.dense_data = nullptr;
     idx->view.n_dense = 0; idx->view.dense_plane = 0; idx->view.dense_p2 = nullptr; idx->view.bit_screen = 0;
     idx->view.exact_wdf = 0; idx->view.dense_wdf0 = nullptr; idx->view.staged_bitmaps = 0; idx->view.reserved_ = 0;
+    idx->facts.has_containers = false; idx->facts.dense_pos = false;
     if (idx->d_dense_p2) { hipFree(idx->d_dense_p2); idx->d_dense_p2 = nullptr; }
     if (idx->d_dense_wdf0) { hipFree(idx->d_dense_wdf0); idx->d_dense_wdf0 = nullptr; }
     idx->term_wdfmax.clear();
@@ -361,7 +362,7 @@ static int build_containers(xgm_index* idx) {
     idx->view.exact_wdf = (!getenv("XGM_NO_EXACT_WDF") && idx->d_dense_wdf0 && idx->d_dense_p2 && plane_off && 5u + SB <= 28u) ? 1u : 0u;
     /* A/B switch XGM_NO_STAGED_BITMAPS: every lane of a plain dense unit asks for the bitmap words of every term < T, as before the two-stage loads */
     idx->view.staged_bitmaps = getenv("XGM_NO_STAGED_BITMAPS") ? 0u : 1u;
-    idx->dense_min_df = (uint64_t)min_avg * n_stripes;
+    idx->facts.has_containers = true; idx->facts.dense_pos = with_pos != 0; idx->facts.dense_min_df = (uint64_t)min_avg * n_stripes;
     hipFree(d_terms); hipFree(d_cnt); hipFree(d_wmax);
     return XGM_OK;
 fail:

@@ -25,7 +25,7 @@
 
 constexpr uint32_t kFlatSq = 128;          /* positional survivors waiting for their test */
 
-/* bytes of the wave's LDS slice a unit uses (the slice of xgm_andw_kernel is larger for any tab_terms >= terms: checked by plan_batch) */
+/* bytes of the wave's LDS slice a unit uses (the slice of xgm_andw_kernel is larger for any tab_terms >= terms: checked by xgm_plan_batch) */
 constexpr size_t kFlatCoreBytes = (size_t)kDenseCap * 12 + (size_t)kDenseT * kDenseSpg * 4;      /* top-k buffer + container offsets */
 __host__ __device__ constexpr size_t flat_wave_bytes(bool phrase, uint32_t terms) {
     return kFlatCoreBytes + (phrase ? (size_t)kFlatSq * (16 + 4 * kDenseT) + (size_t)terms * kPosFast * 64 * 2 : kDenseP2Bytes);

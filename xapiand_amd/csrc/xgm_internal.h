@@ -77,6 +77,17 @@ struct XgmScratch;
 struct XgmBatcher;       /* opt-in micro-batching queue + dispatcher thread (xgm_index_set_batching) */
 struct XgmShardCtx;      /* persistent buffers / streams / RCCL communicator of one shard list (xgm_search_sharded) */
 
+/* What the batch planner (xgm_batch_plan.cc) knows about the acceleration structures of a shard: facts, not device pointers.  xgm_build_dense
+ * fills them where it attaches the structures to idx->view; on a host-only index (XGM_DEVICE_NONE) xgm_debug_set_plan_facts may pretend them. */
+struct XgmPlanFacts {
+    bool has_containers = false;          /* some term has probe containers (view.n_dense != 0) */
+    bool has_flat = false;                /* the terms without containers have flat posting arrays (view.flat_off) */
+    bool dense_pos = false;               /* the containers carry position bases (view.dense_pos) */
+    bool flat_pos = false;                /* the flat arrays carry position offsets (view.flat_pos) */
+    uint64_t dense_min_df = UINT64_MAX;   /* termfreq from which a term has probe containers */
+    uint64_t flat_postings = 0;           /* postings in the flat arrays */
+};
+
 struct xgm_index {
     int device = -1;
     xgm_seg_header hdr{};
@@ -105,9 +116,9 @@ struct xgm_index {
     void* d_flat_did = nullptr;
     void* d_flat_wdf = nullptr;
     void* d_flat_pos = nullptr;
-    uint64_t flat_bytes = 0, flat_postings = 0;
+    uint64_t flat_bytes = 0;
     uint64_t dense_bytes = 0;
-    uint64_t dense_min_df = UINT64_MAX;   /* termfreq from which a term has probe containers */
+    XgmPlanFacts facts;                /* the only stored copy of dense_min_df and flat_postings */
     void* stream = nullptr;            /* hipStream_t                                                */
     bool own_stream = false;
     bool profiling = false;
