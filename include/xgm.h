@@ -838,7 +838,11 @@ int xgm_get_mset_batch_device(xgm_index*, const xgm_query_desc* descs, const xgm
 /* A batch in flight: *_begin plans the work units, uploads, launches the kernels and the copy of the results into pinned host memory
  * the library owns, and returns at once; xgm_batch_end waits for THAT batch and hands out its results — hits [nq][k_stride] (the
  * valid prefix of row q is hdrs[q].n_hits) and hdrs [nq], valid until xgm_batch_release, which returns the batch's buffers to the
- * index.  xgm_batch_poll: 1 when the batch has finished, 0 when not.  Several batches may be in flight per index (each on a stream
+ * index.  The rows may be written by the DEVICE directly: a batch that is one launch of the conjunction kernel on an index bound to a
+ * stream (xgm_index_set_stream) has its last units write hits and headers into that pinned memory, and completes with the kernel —
+ * same layout, same k_stride, and as with the copy only the first n_hits slots of a row are defined.  Read the rows after xgm_batch_end
+ * (or a xgm_batch_poll that returned 1), never before.
+ * xgm_batch_poll: 1 when the batch has finished, 0 when not.  Several batches may be in flight per index (each on a stream
  * of its own unless xgm_index_set_stream bound one): the host plans batch i + 1 while the GPU runs batch i, and consecutive batches
  * overlap on the chip.  This is how a server keeps the device busy AND gets every hit on the host: the dispatcher of
  * xgm_index_set_batching is built on it, bench.py times it.  Begin a batch only while fewer than 8 are unreleased on the index.
@@ -1000,6 +1004,10 @@ int xgm_debug_replay_list(int device, const xgm_hit* list, uint64_t n, uint32_t 
 /* Diagnostics: out3 = {rows with XGM_REPLAY_BATCH_* bits the listing kernel took, rows it declined on the device, rows answered by xgm_search_replay when their
  * batch was collected} of this process. */
 int xgm_debug_batch_replay_info(uint64_t* out3);
+/* Diagnostics: out2 = {batches whose rows the device wrote straight into the pinned rows xgm_batch_end hands out (no download), match launches
+ * that went out without a wait packet for their upload (the host waited for the upload instead: batches with host rows, unless
+ * XGM_UPLOAD_WAIT_ON_STREAM=1)} of this process. */
+int xgm_debug_inflight_info(uint64_t* out2);
 /* Diagnostics: out3 = {batches the dispatcher launched, requests it served, max_batch}. */
 int xgm_debug_batching_info(const xgm_index*, uint64_t* out3);
 /* Diagnostics / bench.py's server leg: n_threads host threads, each answering per_thread queries one at a time through

@@ -188,6 +188,7 @@ _API = [
     ("xgm_debug_replay_info", C.c_int, [_P(C.c_uint64)]),
     ("xgm_debug_replay_list", C.c_int, [C.c_int, _P(Hit), C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64, _P(Hit), _P(ReplayFigures)]),
     ("xgm_debug_batch_replay_info", C.c_int, [_P(C.c_uint64)]),
+    ("xgm_debug_inflight_info", C.c_int, [_P(C.c_uint64)]),
     ("xgm_search_batch", C.c_int, [C.c_void_p, _P(Query), C.c_uint32, C.c_uint32, _P(Hit), _P(ResultHdr)]),
     ("xgm_search_batch_known", C.c_int, [C.c_void_p, _P(Query), C.c_uint32, C.c_uint32, _P(Hit), _P(ResultHdr), _P(C.c_uint64)]),
     ("xgm_search_batch_begin", C.c_int, [C.c_void_p, _P(Query), C.c_uint32, C.c_uint32, _P(C.c_void_p)]),

@@ -90,8 +90,20 @@ struct XgmScratch {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipEvent_t last_stop = nullptr; /* the completion event the LAST launch of the current batch carries itself (run_class_batch: fused wave kernel), or null */
     hipEvent_t ev_done = nullptr;   /* recorded after an asynchronous call that still uses this scratch */
+    hipEvent_t done = nullptr;      /* what completes the scratch's current use: ev_done — or, for a batch whose rows the kernel writes to h_down itself
+                                       (host rows, batch_begin), the stop event its one dispatch carries */
+    bool done_in_pool = false;      /* done is a stop event of idx->prof_events (counted in idx->prof_rows_held until the batch is released) */
+    bool offer_host_rows = false;   /* batch_begin → run_class_batch: the fused merge may write the rows to h_down */
+    bool host_rows = false;         /* run_class_batch → batch_begin: it does — no download */
+    void* h_down_dev = nullptr;     /* device address of h_down (hipHostGetDevicePointer), valid for h_down_mapped */
+    void* h_down_mapped = nullptr;
     bool pending = false;
 };
+
+/* Diagnostics (xgm_debug_inflight_info): [0] batches whose rows the device wrote straight to the caller's pinned buffer, [1] match launches that were
+ * not preceded by a wait packet for their upload (the host waited for it instead). */
+static std::atomic<uint64_t> g_inflight_info[2];
+extern "C" int xgm_debug_inflight_info(uint64_t* out2) { if (!out2) return -1; for (int i = 0; i < 2; ++i) out2[i] = g_inflight_info[i].load(); return 0; }
 
 template <class T>
 static int grow(T** p, size_t* cap, size_t need) {
@@ -129,7 +141,7 @@ static int scratch_acquire(xgm_index* idx, XgmScratch** out) {
         std::vector<XgmScratch*>& pool = idx->scratch_pool;
         for (size_t i = pool.size(); i-- > 0;) {
             XgmScratch* c = pool[i];
-            if (!c->pending || hipEventQuery(c->ev_done) == hipSuccess) {
+            if (!c->pending || hipEventQuery(c->done) == hipSuccess) {
                 c->pending = false;
                 c->inorder = false;
                 pool.erase(pool.begin() + (ptrdiff_t)i);
@@ -148,7 +160,7 @@ static int scratch_acquire(xgm_index* idx, XgmScratch** out) {
     }
     if (*out) return XGM_OK;
     if (wait_for) {
-        hipEventSynchronize(wait_for->ev_done);
+        hipEventSynchronize(wait_for->done);
         wait_for->pending = false;
         wait_for->inorder = false;
         *out = wait_for;
@@ -165,6 +177,7 @@ static int scratch_acquire(xgm_index* idx, XgmScratch** out) {
     hipEventCreate(&s->ev0);
     hipEventCreate(&s->ev1);
     hipEventCreateWithFlags(&s->ev_done, hipEventDisableTiming);
+    s->done = s->ev_done;
     *out = s;
     return XGM_OK;
 }
@@ -193,14 +206,16 @@ static void scratch_destroy(XgmScratch* s) {
 
 /* xgm_index_set_profiling: the next pair of events to record around a kernel (both NULL while profiling is off).  The index keeps the pairs it
  * made, xgm_last_kernel_ms reads and rewinds them; a pair is created when every one is taken. */
-static int next_event_pair(xgm_index* idx, hipEvent_t* start, hipEvent_t* stop) {
+static int next_event_pair(xgm_index* idx, hipEvent_t* start, hipEvent_t* stop, bool hold_for_rows = false) {
     *start = *stop = nullptr;
     if (!idx->profiling) return XGM_OK;
     std::lock_guard<std::mutex> lk(idx->scratch_mu);
+    if (hold_for_rows) ++idx->prof_rows_held;             /* (the stop event will be all that completes the batch: scratch_drop_rows_event) */
     if (idx->prof_used == idx->prof_events.size()) {
         hipEvent_t a = nullptr, b = nullptr;
         if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) {
             if (a) hipEventDestroy(a);
+            if (hold_for_rows) --idx->prof_rows_held;
             return xgm_launch_error("profiling events", 0, "hipEventCreate");
         }
         idx->prof_events.push_back({a, b});
@@ -209,6 +224,26 @@ static int next_event_pair(xgm_index* idx, hipEvent_t* start, hipEvent_t* stop) 
     *stop = (hipEvent_t)idx->prof_events[idx->prof_used].second;
     ++idx->prof_used;
     return XGM_OK;
+}
+
+/* The pairs start over (scratch_mu held).  A batch with host rows in flight has nothing but the stop event of its pair to wait for: the pairs taken so
+ * far complete first, so that a pair handed out again is only ever recorded behind the launch that held it (whoever still waits for it then waits a
+ * little longer, never too short). */
+static void rewind_event_pairs(xgm_index* idx) {
+    if (idx->prof_rows_held)
+        for (size_t i = 0; i < idx->prof_used; ++i) hipEventSynchronize((hipEvent_t)idx->prof_events[i].second);
+    idx->prof_used = 0;
+}
+
+/* A host-rows batch no longer waits for its kernel's stop event: the scratch completes by ev_done again. */
+static void scratch_drop_rows_event(xgm_index* idx, XgmScratch* s) {
+    if (s->done_in_pool) {
+        std::lock_guard<std::mutex> lk(idx->scratch_mu);
+        --idx->prof_rows_held;
+        s->done_in_pool = false;
+    }
+    s->done = s->ev_done;
+    s->host_rows = s->offer_host_rows = false;
 }
 
 /* ------------------------------------------------------------------ index lifetime ----------- */
@@ -380,7 +415,7 @@ extern "C" int xgm_index_set_profiling(xgm_index* idx, int on) {
     std::lock_guard<std::mutex> lk(idx->scratch_mu);
     idx->profiling = (on & 1) != 0;
     idx->tally = (on & 2) != 0;
-    idx->prof_used = 0;
+    rewind_event_pairs(idx);
     return XGM_OK;
 }
 
@@ -398,7 +433,7 @@ extern "C" double xgm_last_kernel_ms(const xgm_index* cidx) {
         float ms = 0.f;
         if (hipEventSynchronize(b) == hipSuccess && hipEventElapsedTime(&ms, a, b) == hipSuccess) { sum += ms; ++n; }
     }
-    idx->prof_used = 0;
+    idx->prof_used = 0;                                   /* (every pair has just been waited for: rewind_event_pairs has nothing to add) */
     return n ? sum / (double)n : -1.0;
 }
 
@@ -605,6 +640,14 @@ static int run_class_batch(xgm_index* idx, XgmScratch* s, hipStream_t stream, co
     static const bool dense_class_old_kernel = getenv("XGM_DENSE_CLASS_OLD_KERNEL") != nullptr;      /* A/B: the same class split, xgm_andw_kernel for both */
     if (dense_class_old_kernel) dense = false;
     const bool fused = bp.fused;
+    /* the wave kernels' dispatch packets carry their events themselves (xgm_launch.h): the profiling pair, and — when the kernel is the
+     * batch's last launch (the fused merge) — the event the download waits for.  XGM_NO_EXT_LAUNCH=1: A/B switch (events recorded around) */
+    static const bool ext_launch = getenv("XGM_NO_EXT_LAUNCH") == nullptr;
+    const bool ext = ext_launch && !dense && (bp.andw || (bp.orw && !bp.orw2));
+    /* host rows (batch_begin offers them): the batch is this ONE launch of the conjunction kernel, whose last units write the final rows — into the
+     * pinned rows xgm_batch_end hands out instead of d_hits / d_hdrs; the stop event its dispatch carries then completes the batch, no download follows */
+    const bool host_rows = s->offer_host_rows && fused && ext && bp.andw && mode == 0 && !rows;
+    s->host_rows = host_rows;
     {
         unsigned char* din_ = (unsigned char*)s->d_in;
         xgm_fuse fu;
@@ -627,6 +670,7 @@ static int run_class_batch(xgm_index* idx, XgmScratch* s, hipStream_t stream, co
             fu.arrive = s->d_arrive; fu.goff = (const uint32_t*)(din_ + o_go); fu.max_possible = (const double*)(din_ + o_mp);
             fu.row_of = rows ? (const uint32_t*)(din_ + o_ro) : nullptr;
             fu.hits = d_hits; fu.hdrs = d_hdrs; fu.k_stride_out = k_stride;
+            if (host_rows) { fu.hits = (xgm_hit*)s->h_down_dev; fu.hdrs = (xgm_result_hdr*)(fu.hits + (size_t)nq * k_stride); }
         }
         if (list) fu.goff = (const uint32_t*)(din_ + o_go);      /* (xgm_andw_list_kernel: the first unit slot of every query) */
         memcpy(hin + o_fu, &fu, sizeof fu);
@@ -634,6 +678,7 @@ static int run_class_batch(xgm_index* idx, XgmScratch* s, hipStream_t stream, co
     const uint64_t t_cp = now_ns();
     g_host_ns[4] += t_cp - t_st;
     bool hist_zeroed = false;
+    bool upload_awaited = false;                             /* the host waits for the upload before it launches: no wait packet on `stream` */
     if (stream != s->stream && !s->inorder) {
         /* asynchronous caller: the inputs go up on the scratch's own stream, so the copy overlaps the
          * kernels of the previous batch still running on the caller's stream */
@@ -648,7 +693,15 @@ static int run_class_batch(xgm_index* idx, XgmScratch* s, hipStream_t stream, co
         }
         HIP_TRY(hipMemcpyAsync(s->d_in, hin, in_bytes, hipMemcpyHostToDevice, s->stream));
         HIP_TRY(hipEventRecord(s->ev0, s->stream));
-        HIP_TRY(hipStreamWaitEvent(stream, s->ev0, 0));
+        /* the kernels of consecutive batches run back to back on `stream`: a wait packet for the upload would be one more packet the command processor
+         * works through between two of them.  The upload (a few hundred KB) is done long before the kernel ahead of this one; the host finishes
+         * its own work first and then waits for ev0 itself (below).  XGM_UPLOAD_WAIT_ON_STREAM=1: A/B switch, the packet.
+         * Only for a batch with host rows: a batch that downloads leaves "wait for the kernel, copy, record" on its scratch's stream, the scratch
+         * streams share hardware queues, and an upload queued behind such a wait is done only when the kernel AHEAD has ended — the host would
+         * sit out that kernel before it launches (measured: the host-side wait without host rows runs 2.7 % below the packet) */
+        static const bool wait_on_stream = getenv("XGM_UPLOAD_WAIT_ON_STREAM") != nullptr;
+        if (wait_on_stream || !host_rows) HIP_TRY(hipStreamWaitEvent(stream, s->ev0, 0));
+        else upload_awaited = true;
     } else {
         HIP_TRY(hipMemcpyAsync(s->d_in, hin, in_bytes, hipMemcpyHostToDevice, stream));
     }
@@ -672,7 +725,8 @@ static int run_class_batch(xgm_index* idx, XgmScratch* s, hipStream_t stream, co
     L.tally = idx->tally;
     L.cand = s->d_cand; L.ghdr = s->d_ghdr;
     hipEvent_t pe0 = nullptr, pe1 = nullptr;
-    if ((rc = next_event_pair(idx, &pe0, &pe1))) return rc;
+    if ((rc = next_event_pair(idx, &pe0, &pe1, host_rows))) return rc;
+    if (host_rows && pe1) s->done_in_pool = true;
     idx->last_kernel = xgm_plan_kernel_name(bp, mode, dense).name;
     idx->last_ghdr = s->d_ghdr; idx->last_n_work = bp.n_work;        /* xgm_last_batch_traffic */
     idx->last_tallied = idx->tally;                                  /* (the slots below describe this batch, or no batch at all) */
@@ -691,16 +745,22 @@ static int run_class_batch(xgm_index* idx, XgmScratch* s, hipStream_t stream, co
         L.hist = s->d_hist;
     }
     if (fused || list) L.fuse = (const xgm_fuse*)(din + o_fu);
-    /* the wave kernels' dispatch packets carry their events themselves (xgm_launch.h): the profiling pair, and — when the kernel is the
-     * batch's last launch (the fused merge) — the event the download waits for.  XGM_NO_EXT_LAUNCH=1: A/B switch (events recorded around) */
-    static const bool ext_launch = getenv("XGM_NO_EXT_LAUNCH") == nullptr;
-    const bool ext = ext_launch && !dense && (bp.andw || (bp.orw && !bp.orw2));
     s->last_stop = nullptr;
     if (ext) {
         L.ev_start = pe0;
         L.ev_stop = pe1 ? pe1 : (fused ? s->ev1 : nullptr);
         if (fused) s->last_stop = L.ev_stop;
+        if (host_rows) s->done = L.ev_stop;                  /* ONE stop event: the profiling pair's, else the scratch's ev1 */
         pe0 = pe1 = nullptr;
+    }
+    if (upload_awaited) {
+        /* a bounded spin (the copy takes 10-20 us and was enqueued before the host's remaining work), then the blocking wait */
+        const uint64_t t_spin = now_ns();
+        hipError_t eu = hipEventQuery(s->ev0);
+        while (eu == hipErrorNotReady && now_ns() - t_spin < 200000ull) eu = hipEventQuery(s->ev0);
+        if (eu == hipErrorNotReady) eu = hipEventSynchronize(s->ev0);
+        if (eu != hipSuccess) return xgm_launch_error("upload", (int)eu, hipGetErrorString(eu));
+        ++g_inflight_info[1];
     }
     if (pe0) HIP_TRY(hipEventRecord(pe0, stream));
     if ((rc = all ? xgm_launch_andw_all(L, all_out, stream) : list ? xgm_launch_andw_list(L, stream) : dense ? xgm_launch_dense(L, stream) : bp.andw ? xgm_launch_andw(L, stream)
@@ -872,6 +932,20 @@ static int batch_begin(xgm_index* idx, const xgm_query* qs, uint32_t nq, uint32_
         unsigned long long* d_extra = has_extra ? reinterpret_cast<unsigned long long*>(s->d_hits + n_hit + (size_t)nq * 2) : nullptr;
         const size_t down = n_hit * sizeof(xgm_hit) + (size_t)nq * sizeof(xgm_result_hdr) + (has_extra ? (size_t)nq * 8 : 0);
         if ((rc = grow_pinned(&s->h_down, &s->cap_down, down))) break;
+        /* host rows: a batch bound to the index's stream whose rows nothing on the host amends (no replay bits) offers its pinned rows to the launch;
+         * run_class_batch takes the offer when the batch is one fused launch of the conjunction kernel.  XGM_NO_HOST_ROWS=1: A/B switch */
+        static const bool no_host_rows = getenv("XGM_NO_HOST_ROWS") != nullptr;
+        s->host_rows = false;
+        s->offer_host_rows = !no_host_rows && stream != s->stream && !s->inorder && !has_extra;
+        if (s->offer_host_rows && s->h_down_mapped != s->h_down) {
+#if defined(XGM_EMU)
+            s->h_down_dev = s->h_down;                       /* (the emulated device shares the host's address space) */
+#else
+            const hipError_t em = hipHostGetDevicePointer(&s->h_down_dev, s->h_down, 0);
+            if (em != hipSuccess) { rc = xgm_launch_error("hipHostGetDevicePointer", (int)em, hipGetErrorString(em)); break; }
+#endif
+            s->h_down_mapped = s->h_down;
+        }
         if (has_extra) {
             const hipError_t ez = hipMemsetAsync(d_extra, 0, (size_t)nq * 8, stream);
             if (ez != hipSuccess) { rc = xgm_launch_error("hipMemsetAsync", (int)ez, hipGetErrorString(ez)); break; }
@@ -882,7 +956,11 @@ static int batch_begin(xgm_index* idx, const xgm_query* qs, uint32_t nq, uint32_
          * (XGM_COPY_ON_BATCH_STREAM=1: A/B switch, the copy in stream order) */
         static const bool copy_in_order = getenv("XGM_COPY_ON_BATCH_STREAM") != nullptr;
         hipError_t e = hipSuccess;
-        if (stream != s->stream && !copy_in_order && !s->inorder) {
+        s->offer_host_rows = false;
+        if (s->host_rows) {
+            /* the kernel wrote the rows where xgm_batch_end reads them and s->done is its own stop event: nothing more goes on any stream */
+            ++g_inflight_info[0];
+        } else if (stream != s->stream && !copy_in_order && !s->inorder) {
             hipEvent_t after = s->last_stop;                       /* the batch's one launch carries its completion event itself */
             if (!after) { after = s->ev1; e = hipEventRecord(after, stream); }
             if (e == hipSuccess) e = hipStreamWaitEvent(s->stream, after, 0);
@@ -897,6 +975,7 @@ static int batch_begin(xgm_index* idx, const xgm_query* qs, uint32_t nq, uint32_
     if (rc) {
         hipStreamSynchronize(stream);              /* whatever was enqueued no longer uses the scratch */
         hipStreamSynchronize(s->stream);
+        scratch_drop_rows_event(idx, s);
         scratch_release(idx, s);
         return rc;
     }
@@ -965,7 +1044,7 @@ extern "C" int xgm_batch_end(xgm_inflight* f, const xgm_hit** hits, const xgm_re
     if (!f) return xgm_set_error(XGM_E_INVALID, "null argument");
     if (!f->ended) {
         f->ended = true;
-        hipError_t e = hipEventSynchronize(f->s->ev_done);
+        hipError_t e = hipEventSynchronize(f->s->done);
         if (e != hipSuccess) f->rc_end = xgm_launch_error("batch completion", (int)e, hipGetErrorString(e));
         else if (f->has_extra) f->rc_end = batch_host_replays(f);
     }
@@ -985,12 +1064,13 @@ extern "C" int xgm_batch_known(xgm_inflight* f, const uint64_t** known) {
 extern "C" int xgm_batch_poll(xgm_inflight* f) {
     if (!f) return xgm_set_error(XGM_E_INVALID, "null argument");
     if (f->ended) return 1;
-    return hipEventQuery(f->s->ev_done) == hipSuccess ? 1 : 0;
+    return hipEventQuery(f->s->done) == hipSuccess ? 1 : 0;
 }
 
 extern "C" void xgm_batch_release(xgm_inflight* f) {
     if (!f) return;
-    if (!f->ended) hipEventSynchronize(f->s->ev_done);
+    if (!f->ended) hipEventSynchronize(f->s->done);
+    scratch_drop_rows_event(f->idx, f->s);
     scratch_release(f->idx, f->s);
     delete f;
 }

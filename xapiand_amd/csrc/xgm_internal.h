@@ -131,6 +131,9 @@ struct xgm_index {
     std::vector<uint32_t> last_staged_slots;   /* tallying launches: the header slots of the batch's plain dense units (xgm_last_batch_bitmap_skipped: c_pad[0] is theirs alone) */
     std::vector<std::pair<void*, void*>> prof_events;   /* hipEvent_t pairs around the match kernel */
     size_t prof_used = 0;
+    uint32_t prof_rows_held = 0;       /* batches in flight whose ONLY completion event is a stop event of prof_events (host rows, xgm_api.cc: batch_begin):
+                                          a rewind of the pairs waits for those events first, so that a pair is never recorded again under a batch that
+                                          still has to wait for it.  Under scratch_mu */
     std::mutex scratch_mu;
     std::vector<XgmScratch*> scratch_pool;
     uint32_t scratch_total = 0;        /* scratches created so far (pooled + in use) */
