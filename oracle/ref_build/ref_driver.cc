@@ -570,26 +570,32 @@ int cmd_compact(int argc, char** argv) {
  * positions, boolean terms (wdf 0), long posting lists (several chunks). */
 /* build_postings <dbdir> <file>: documents spelled out posting by posting — one line per document, docids 1, 2, ... in file order,
  * "term:pos term:pos ..." (add_posting each: several terms may share a position, what a schema that indexes a word's prefixed and
- * unprefixed forms does).  For NEAR over co-located terms (nearpostlist.cc:106-140; tests/helpers.py coloc_postings). */
+ * unprefixed forms does).  For NEAR over co-located terms (nearpostlist.cc:106-140; tests/helpers.py coloc_postings) and the crafted
+ * corpus of the nested-query edges (tree_edge_postings), whose deleted documents are lines that hold "-" alone. */
 int cmd_build_postings(int argc, char** argv) {
     if (argc < 4) return 2;
     Xapian::WritableDatabase db(argv[2], Xapian::DB_CREATE_OR_OVERWRITE | Xapian::DB_BACKEND_GLASS | Xapian::DB_NO_SYNC);
     std::ifstream in(argv[3]);
     std::string line;
     unsigned n = 0;
+    std::vector<Xapian::docid> gone;
     while (std::getline(in, line)) {
         Xapian::Document doc;
         std::istringstream ss(line);
         std::string tok;
-        while (ss >> tok) {
+        while (line != "-" && ss >> tok) {
             const size_t c = tok.rfind(':');
             if (c == std::string::npos) return 2;
             doc.add_posting(tok.substr(0, c), (Xapian::termpos)std::stoul(tok.substr(c + 1)));
         }
-        db.add_document(doc);
+        if (line == "-") doc.add_posting("-", 1);               /* a line "-": the docid is used up and the document deleted — a gap */
+        const Xapian::docid did = db.add_document(doc).did;
+        if (line == "-") gone.push_back(did);
         if (++n % 1000 == 0) db.commit();
     }
     db.commit();
+    for (Xapian::docid did : gone) db.delete_document(did);     /* (once committed, as cmd_build_misc deletes) */
+    if (!gone.empty()) db.commit();
     printf("{\"doccount\": %u, \"lastdocid\": %u}\n", db.get_doccount(), db.get_lastdocid());
     return 0;
 }

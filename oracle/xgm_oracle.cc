@@ -980,7 +980,8 @@ int run_query(Index* ix, const QueryIn& q, Result* out) {
  * Weights: multiandpostlist.cc:150-160, orpostlist.cc:94-103, andmaybepostlist.cc:57-64, leafpostlist.cc:57-65.
  * count_matching_subqs: leafpostlist.cc:88-91 (weighted leaves), synonym = 1, sums / left side as in each PostList.
  * Evaluation is exhaustive, document at a time over dense per-term wdf arrays: test sizes only. */
-enum { T_TERM = 0, T_AND = 1, T_OR = 2, T_AND_NOT = 3, T_AND_MAYBE = 4, T_FILTER = 5, T_SYNONYM = 6, T_SCALE = 7 };
+enum { T_TERM = 0, T_AND = 1, T_OR = 2, T_AND_NOT = 3, T_AND_MAYBE = 4, T_FILTER = 5, T_SYNONYM = 6, T_SCALE = 7,
+       T_WILDCARD = 8, T_WILDCARD_OR = 9 };      /* OP_WILDCARD over its expansion (the caller lists it, in term order): OP_SYNONYM / OP_OR combiner */
 
 struct TreeIn {
     uint32_t n_terms; const char* const* terms; const uint32_t* term_len; const uint32_t* wqf;
@@ -1030,6 +1031,14 @@ struct TreeEval {
         }
         n.wt.init(N, tf_syn, avg, 1u, factor);
         if (n.weighted) { ++total_subqs; n.maxw = n.wt.maxpart(doclen_ub, ix->doclen_lb); }     /* Weight::init_ synonym case: wdf bound = doclength bound */
+        /* LocalSubMatch::make_synonym_postlist, localsubmatch.cc:205-209: a WEIGHTED synonym over members none of which the shard holds
+         * (or_pl->get_termfreq_max() == 0) is NO postlist — counted as a subquery (QuerySynonym::postlist), but absent from whatever holds it;
+         * an unweighted one is its BoolOrPostList (do_synonym, :1827-1832) */
+        if (n.weighted) {
+            bool any = false;
+            for (int t : terms) any = any || tf_local[t] != 0;
+            if (!any) return -1;
+        }
         return add(std::move(n));
     }
     int mand(std::vector<int> ctx) {
@@ -1072,27 +1081,36 @@ struct TreeEval {
             sift_down(h, h.size(), 0);
         }
     }
-    void sub_and_like(int a, std::vector<int>& ctx, double factor) {
+    /* No postlist (-1) where the reference has a NULL one: AndContext::add_postlist empties the context and the lowering of the AND STOPS
+     * there (queryinternal.cc:564-571, 2092-2103: the subqueries after it are never counted), Context::add_postlist of an OR context
+     * skips it (:198-201), AND_NOT / AND_MAYBE / FILTER are nothing without their left side and are their left side without the right
+     * (:2208-2283). */
+    bool sub_and_like(int a, std::vector<int>& ctx, double factor) {
         const ANode& n = ast[a];
-        if (n.kind == T_AND) { for (int k : n.kids) sub_and_like(k, ctx, factor); return; }
-        if (n.kind == T_FILTER) { for (int k : n.kids) { sub_and_like(k, ctx, factor); factor = 0.0; } return; }
-        ctx.push_back(postlist(a, factor));
+        if (n.kind == T_AND) { for (int k : n.kids) if (!sub_and_like(k, ctx, factor)) return false; return true; }
+        if (n.kind == T_FILTER) { for (int k : n.kids) { if (!sub_and_like(k, ctx, factor)) return false; factor = 0.0; } return true; }
+        const int x = postlist(a, factor);
+        if (x < 0) { ctx.clear(); return false; }
+        ctx.push_back(x);
+        return true;
     }
     void sub_or_like(int a, std::vector<int>& ctx, double factor) {
         const ANode& n = ast[a];
         if (n.kind == T_OR) { for (int k : n.kids) sub_or_like(k, ctx, factor); return; }
-        ctx.push_back(postlist(a, factor));
+        const int x = postlist(a, factor);
+        if (x >= 0) ctx.push_back(x);
     }
     int postlist(int a, double factor) {
         const ANode& n = ast[a];
         switch (n.kind) {
         case T_TERM: return leaf(n.term, factor);
         case T_SCALE: return postlist(n.kids[0], factor * n.scale);
-        case T_AND: { std::vector<int> ctx; sub_and_like(a, ctx, factor); return mand(ctx); }
-        case T_FILTER: { int l = postlist(n.kids[0], factor); int r = postlist(n.kids[1], 0.0); return mand({l, r}); }
+        case T_AND: { std::vector<int> ctx; return sub_and_like(a, ctx, factor) ? mand(ctx) : -1; }
+        case T_FILTER: { int l = postlist(n.kids[0], factor); if (l < 0) return -1; int r = postlist(n.kids[1], 0.0); return r < 0 ? -1 : mand({l, r}); }
         case T_OR: { std::vector<int> ctx; sub_or_like(a, ctx, factor); return or_tree(ctx); }
         case T_AND_NOT: {
             int l = postlist(n.kids[0], factor);
+            if (l < 0) return -1;
             std::vector<int> ctx;
             for (size_t i = 1; i < n.kids.size(); ++i) sub_or_like(n.kids[i], ctx, 0.0);
             int r = or_tree(ctx);
@@ -1106,6 +1124,7 @@ struct TreeEval {
         }
         case T_AND_MAYBE: {
             int l = postlist(n.kids[0], factor);
+            if (l < 0) return -1;
             if (factor == 0.0) return l;
             std::vector<int> ctx;
             for (size_t i = 1; i < n.kids.size(); ++i) sub_or_like(n.kids[i], ctx, factor);
@@ -1119,6 +1138,16 @@ struct TreeEval {
             for (int k : n.kids) terms.push_back(ast[k].term);
             if (terms.size() == 1) return leaf(terms[0], factor);          /* QuerySynonym::done: a synonym of one term is the term */
             return synonym(terms, factor);
+        }
+        case T_WILDCARD: {                                                 /* QueryWildcard::postlist, OP_SYNONYM combiner: a SynonymPostList even over one term */
+            std::vector<int> terms;
+            for (int k : n.kids) terms.push_back(ast[k].term);
+            return synonym(terms, factor);
+        }
+        case T_WILDCARD_OR: {                                              /* ... OP_OR combiner: an OrContext of its own, never flattened into the parent's */
+            std::vector<int> ctx;
+            for (int k : n.kids) ctx.push_back(leaf(ast[k].term, factor));
+            return or_tree(ctx);
         }
         }
         return -1;
@@ -1180,7 +1209,8 @@ int run_tree(Index* ix, const TreeIn& q, Result* out, uint32_t* total_subqs_out)
             n.kids.assign(stack.end() - ar, stack.end());
             stack.resize(stack.size() - ar);
             if (n.kind == T_SCALE) n.scale = q.scale[i];
-            if (n.kind == T_SYNONYM) for (int k : n.kids) if (ev.ast[k].kind != T_TERM) return -1;
+            if (n.kind > T_WILDCARD_OR) return -1;
+            if (n.kind == T_SYNONYM || n.kind == T_WILDCARD || n.kind == T_WILDCARD_OR) for (int k : n.kids) if (ev.ast[k].kind != T_TERM) return -1;
             if ((n.kind == T_FILTER) && ar != 2) return -1;
             if ((n.kind == T_AND_NOT || n.kind == T_AND_MAYBE) && ar < 2) return -1;
         }
@@ -1208,7 +1238,11 @@ int run_tree(Index* ix, const TreeIn& q, Result* out, uint32_t* total_subqs_out)
     }
     for (uint32_t d = 1; d <= ix->lastdocid; ++d) ev.doclen_ub = std::max(ev.doclen_ub, ix->doclen_dense[d]);
     const int root = ev.postlist(stack[0], 1.0);
-    if (root < 0) return -1;
+    if (total_subqs_out) *total_subqs_out = ev.total_subqs;
+    if (root < 0) {          /* no postlist at all: the empty MSet, max_possible 0 (Matcher::get_mset) */
+        out->hits.clear(); out->matches = 0; out->max_possible = 0.0; out->max_attained = 0.0; out->max_subqs = 0;
+        return 0;
+    }
     uint32_t docs = ix->doccount;
     uint32_t first = std::min(q.first, docs);
     uint32_t maxitems = std::min(q.maxitems, docs - first);

@@ -9,6 +9,8 @@ Config C1 of BASELINE.json: 10k-doc synthetic index, 3-term AND BM25 top-10 thro
 other fixtures cover OR-5 top-100, full-result PHRASE, paging (first > 0), the two-sided operators
 (AND_NOT / AND_MAYBE / FILTER), a 4-shard index run through Xapiand's prepare/merge protocol, and — groundwork of the
 next widening row — the value sorts (sort keys recorded) and a ValueCountMatchSpy's counts over the whole match.
+tree_edges.json: the nested queries of helpers.tree_edge_cases() on the crafted corpus of helpers.tree_edge_postings(), a top-10 page and the
+whole match of each (`python tests/golden/make_golden.py tree_edges` writes that fixture alone).
 """
 import json
 import os
@@ -53,6 +55,39 @@ def run(tmp, dbs, queries, tag, full_ranking_check=False):
     return out
 
 
+LONG_PAGE = 100
+
+
+def hits_digest(hits):
+    """A page too long to spell out: the SHA-256 of its lines "docid weight-as-hex-float percent"."""
+    import hashlib
+    return hashlib.sha256("".join("%d %s %d\n" % (d, w, p) for d, w, p in hits).encode()).hexdigest()
+
+
+def tree_edges(tmp):
+    """The crafted nested-query cases through the compiled reference: a top-10 page and the whole match of every case, under the same
+    full-ranking rule as nested_trees (a page that is not the prefix of the reference's own whole ranking is recorded from that ranking and
+    flagged — allowed only under an OR over AND_NOT / AND_MAYBE children, and for one case in eight at the most).  Whole matches of more than
+    LONG_PAGE documents are recorded as their length and hits_digest."""
+    post, doclen = H.tree_edge_postings()
+    pf, db = os.path.join(tmp, "edges.txt"), os.path.join(tmp, "dbe")
+    H.write_postings_file(pf, post, doclen)
+    H.xapian_ref("build_postings", db, pf)
+    cases = H.tree_edge_cases()
+    results = (run(tmp, [db], H.tree_edge_queries(cases, 0, 10), "edges10", full_ranking_check=True) +
+               run(tmp, [db], H.tree_edge_queries(cases, 0, H.TREE_EDGE_LASTDOCID), "edgesall", full_ranking_check=True))
+    flagged = sorted({r["query"]["name"] for r in results if r["query"].get("reference_quirk")})
+    assert all(H.tree_has_or_over_sided(dict(cases)[n]) for n in flagged), flagged
+    assert len(flagged) * 8 <= len(cases), flagged
+    for r in results:
+        if len(r["hits"]) > LONG_PAGE:
+            r["n_hits"], r["hits_sha256"] = len(r["hits"]), hits_digest(r["hits"])
+            del r["hits"]
+    with open(os.path.join(HERE, "tree_edges.json"), "w") as f:
+        json.dump(dict(tree_edges=dict(lastdocid=H.TREE_EDGE_LASTDOCID), n_shards=1, results=results), f, indent=0)
+    print("tree_edges: %d cases, flagged as reference quirks: %s" % (len(cases), flagged))
+
+
 def sharded(tmp, corpus, n_shards):
     """Xapiand's per-shard protocol (prepare_mset / add_prepared_mset / get_mset per shard / unshard_docids + merge_mset, handler.cc:1532-1549)
     over n_shards docid-interleaved shards (multi.h:38-73) through the compiled reference: 4 shards (rounds 1-4) and — C4's shape, the
@@ -72,6 +107,10 @@ def main():
         with tempfile.TemporaryDirectory() as tmp:
             sharded(tmp, dict(seed=H.CORPUS_SEED, n_docs=N_DOCS, vocab=VOCAB, len_lo=50, len_hi=150), 8)
         print("sharded8 fixture written to", HERE)
+        return
+    if sys.argv[1:] == ["tree_edges"]:
+        with tempfile.TemporaryDirectory() as tmp:
+            tree_edges(tmp)
         return
     with tempfile.TemporaryDirectory() as tmp:
         db = os.path.join(tmp, "db")
@@ -118,6 +157,7 @@ def main():
         H.xapian_ref("build_postings", dbc, pf)
         with open(os.path.join(HERE, "near_colocated.json"), "w") as f:
             json.dump(dict(coloc=dict(seed=0xC010C, n_docs=600), n_shards=1, results=run(tmp, [dbc], H.coloc_near_queries(), "coloc")), f, indent=0)
+        tree_edges(tmp)
         sharded(tmp, corpus, 4)
         sharded(tmp, corpus, 8)
     print("golden fixtures written to", HERE)

@@ -586,7 +586,7 @@ def write_postings_file(path, post, doclen):
             docs.setdefault(d, []).extend("%s:%d" % (t, p) for p in pp)
     with open(path, "w") as f:
         for d in range(1, max(doclen) + 1):
-            f.write(" ".join(sorted(docs.get(d, []))) + "\n")
+            f.write((" ".join(sorted(docs.get(d, []))) if d in doclen else "-") + "\n")      # "-": a deleted document, its docid a gap
 
 
 def coloc_near_queries():
@@ -698,9 +698,13 @@ def oracle_search_batch(corpus, queries, first, maxitems, n_threads=None, refere
 
 # ---- nested queries: a tree of tuples <-> the post-order token form of xapian_ref's "RPN" queries ----
 #   tree := "term" | ("term", wqf) | ("AND", t, t, ...) | ("OR", ...) | ("SYN", term, ...) | ("AND_NOT", left, right...) |
-#           ("AND_MAYBE", left, right...) | ("FILTER", left, right) | ("SCALE", factor, t)
-T_KIND = {"TERM": 0, "AND": 1, "OR": 2, "AND_NOT": 3, "AND_MAYBE": 4, "FILTER": 5, "SYN": 6, "SCALE": 7}
+#           ("AND_MAYBE", left, right...) | ("FILTER", left, right) | ("SCALE", factor, t) |
+#           ("WILD", prefix, term, ...) | ("WILD_OR", prefix, term, ...): OP_WILDCARD "prefix*" with the OP_SYNONYM / OP_OR combiner; the terms
+#           are its expansion — every term of the corpus under the prefix, in term order: the reference expands the prefix itself (the driver's
+#           "~prefix,0,E,S" / "~prefix,0,E,O" tokens), the device and the oracle are handed the list
+T_KIND = {"TERM": 0, "AND": 1, "OR": 2, "AND_NOT": 3, "AND_MAYBE": 4, "FILTER": 5, "SYN": 6, "SCALE": 7, "WILD": 8, "WILD_OR": 9}
 _RPN_SIGN = {"AND": "&", "OR": "|", "SYN": "=", "AND_NOT": "-", "AND_MAYBE": "?"}
+_WILD = ("WILD", "WILD_OR")
 
 
 def tree_from_json(t):
@@ -719,6 +723,8 @@ def tree_rpn(tree):
     op = tree[0]
     if op == "SCALE":
         return tree_rpn(tree[2]) + ["*%r" % float(tree[1])]
+    if op in _WILD:
+        return ["~%s,0,E,%s" % (tree[1], "S" if op == "WILD" else "O")]
     toks = [x for k in tree[1:] for x in tree_rpn(k)]
     if op == "FILTER":
         return toks + ["!"]
@@ -742,9 +748,10 @@ def tree_program(tree):
             walk(t[2])
             ops.append((T_KIND["SCALE"], 1, 0, float(t[1])))
             return
-        for k in t[1:]:
+        kids = t[2:] if op in _WILD else t[1:]
+        for k in kids:
             walk(k)
-        ops.append((T_KIND[op], len(t) - 1, 0, 1.0))
+        ops.append((T_KIND[op], len(kids), 0, 1.0))
     walk(tree)
     return terms, wqf, ops
 
@@ -824,3 +831,244 @@ def gen_tree_queries(n_queries, rank_lo=1, rank_hi=300, seed=QUERY_SEED):
             tree = ("AND_MAYBE", ("SYN", a[0], a[1]), ("SYN", a[2], a[3], a[4]), a[5])
         qs.append(dict(op="RPN", tree=tree, terms=tree_rpn(tree), first=0, maxitems=10, window=0))
     return qs
+
+
+def tree_percentages(page, hdr, total_subqs):
+    """MSet::convert_to_percent over the rows of a page, with percent_scale_factor = matched / total weighted subqueries of the best document
+    / its weight (hdr.max_subqs, hdr.max_attained: of the WHOLE match) — what the reference driver prints beside every hit of an RPN query."""
+    scale = hdr.max_subqs / float(total_subqs) / hdr.max_attained * 100.0
+    return [min(100, max(1, int(w * scale + 100.0 * 2.220446049250313e-16))) if w > 0 else 0 for _, w, _ in page]
+
+
+# ---- nested queries at the edges of the lowering and of the node program: a crafted corpus, an explicit table of cases ----
+
+TREE_EDGE_LASTDOCID, TREE_EDGE_GAP = 2600, (1301, 1340)          # docids 1301 .. 1340 are deleted documents
+TREE_EDGE_M = ["m%d" % i for i in range(16)]
+TREE_EDGE_ABSENT = ("nosuch1", "nosuch2")
+
+
+def synonym_estimate(dfs, db_size):
+    """TreePlanner::synonym's estimate of a group (BoolOrPostList::get_termfreq_est): the members taken for independent."""
+    scale = 1.0 / db_size
+    p = dfs[0] * scale
+    for df in dfs[1:]:
+        pi = df * scale
+        p += pi - p * pi
+    return int(p * db_size + 0.5)
+
+
+def or_estimate(a, b, db_size):
+    """est_or: OrPostList::get_termfreq_est of two children."""
+    return int(a + b - (float(a) * b / db_size) + 0.5)
+
+
+def tree_edge_postings(seed=0x7EE0ED6E):
+    """The corpus of the nested-query edge cases: 2 560 documents at docids 1 .. 2600 with a gap of 40 deleted ones in the middle (11 stripes of
+    256, 3 of 1024).  Returns (postings {term: [(did, wdf, [1 .. wdf])]}, doclen {did: length}) for ManualCorpus and write_postings_file.
+      eqA eqB eqC eqD   df 96 each out of one pool of 160 documents (they overlap in part), wdf patterns of their own: ties in every order
+      eqS1 eqS2, eqL    df(eqL) == the ESTIMATE of SYN(eqS1, eqS2);  eqO: df == the estimate of OR(eqA, eqB) — asserted below
+      all               every document;  one: df 1 (docid 500);  first: docid 1;  last: docid 2600
+      w254a w254b       wdf 254 in the two documents they share (500, 1800): their wdf bound stays 254, the group's sum is 508
+      w255, w300        a wdf of 255 (in 500) and of 300 (in 1800): terms of the 16-bit tables
+      m0 .. m15         forty shared documents, and 5 + 3 i of their own
+      o00 .. o23        df 3 .. 1500 in geometric steps, wdf 1 .. 5
+    nosuch1 / nosuch2 (TREE_EDGE_ABSENT) have no postings.  Every choice is a function of hash64: the same corpus on every Python."""
+    last, gap = TREE_EDGE_LASTDOCID, TREE_EDGE_GAP
+    live = [d for d in range(1, last + 1) if not gap[0] <= d <= gap[1]]
+    post = {}
+
+    def pick(tag, pool, n):
+        return sorted(sorted(pool, key=lambda d: hash64(seed, tag, d))[:n])
+
+    def put(term, docs, wdf):
+        post[term] = [(d, wdf(d), list(range(1, wdf(d) + 1))) for d in docs]
+    put("all", live, lambda d: 1 + d % 3)
+    pool = pick(1, live, 320)
+    pool_eq = pick(2, pool, 160)              # (four sets of 96 out of 160: some twenty documents hold all four)
+    put("eqA", pick(10, pool_eq, 96), lambda d: 1 + d % 3)
+    put("eqB", pick(11, pool_eq, 96), lambda d: 1 + d % 2)
+    put("eqC", pick(12, pool_eq, 96), lambda d: 1 + (d // 3) % 3)
+    put("eqD", pick(13, pool_eq, 96), lambda d: 2 if d % 5 == 0 else 1)
+    put("eqS1", pick(20, pool, 64), lambda d: 1 + d % 2)
+    put("eqS2", pick(21, pool, 80), lambda d: 1 + (d // 2) % 2)
+    put("eqL", pick(22, pool, 142), lambda d: 1)
+    put("eqO", pick(23, pool, 188), lambda d: 1)
+    put("one", [500], lambda d: 3)
+    put("first", [1], lambda d: 2)
+    put("last", [last], lambda d: 2)
+    put("w254a", [500, 1800], lambda d: 254)
+    put("w254b", [500, 1800], lambda d: 254)
+    put("w255", [500, 1900], lambda d: 255 if d == 500 else 7)
+    put("w300", [640, 1800], lambda d: 300 if d == 1800 else 2)
+    shared = [100 + 60 * j for j in range(40)]
+    assert not any(gap[0] <= d <= gap[1] for d in shared)
+    rest = [d for d in live if d not in shared]
+    for i, m in enumerate(TREE_EDGE_M):
+        put(m, sorted(shared + pick(40 + i, rest, 5 + 3 * i)), lambda d, i=i: 1 + (d + i) % 2)
+    for i in range(24):
+        put("o%02d" % i, pick(100 + i, live, int(round(3 * 500 ** (i / 23.0)))), lambda d, i=i: 1 + hash64(seed, 200 + i, d) % 5)
+    doclen = {d: 0 for d in live}
+    for pl in post.values():
+        for d, w, _ in pl:
+            doclen[d] += w
+    db_size = len(live)
+    assert db_size == 2560 and len(post["all"]) == db_size and not set(TREE_EDGE_ABSENT) & set(post)
+    # the ties the cases rest on: equal df, and a leaf whose df IS a sub-tree's estimate
+    assert len({len(post[t]) for t in ("eqA", "eqB", "eqC", "eqD")}) == 1
+    assert len(post["eqL"]) == synonym_estimate([len(post["eqS1"]), len(post["eqS2"])], db_size) == synonym_estimate([len(post["eqS2"]), len(post["eqS1"])], db_size)
+    assert len(post["eqO"]) == or_estimate(len(post["eqA"]), len(post["eqB"]), db_size)
+    return post, doclen
+
+
+def tree_edge_prefix(prefix):
+    """The expansion of "prefix*" over the crafted corpus, in term order (the terms are fixed names: no corpus is built for this)."""
+    names = (["all", "one", "first", "last", "eqA", "eqB", "eqC", "eqD", "eqS1", "eqS2", "eqL", "eqO", "w254a", "w254b", "w255", "w300"] + TREE_EDGE_M +
+             ["o%02d" % i for i in range(24)])
+    return sorted(t for t in names if t.startswith(prefix))
+
+
+def tree_edge_cases():
+    """[(name, tree)]: the nested queries at the edges of plan_tree's lowering and of the match kernel's node program, on tree_edge_postings().
+    The name's first word says which edge: tie (equal estimates), root (the root is a group), one (AND / OR of one child), flat (the flattening
+    rules), sided (AND_NOT / AND_MAYBE with several right-hand children), absent (terms the shard does not hold), all (a term in every
+    document), width (synonym groups at the wdf tables' width), limit (16 terms, 40 ops), wild (OP_WILDCARD), quirk (an OR over AND_NOT /
+    AND_MAYBE children: where the reference may lose documents)."""
+    A, B, C, D, S1, S2, L, O = "eqA", "eqB", "eqC", "eqD", "eqS1", "eqS2", "eqL", "eqO"
+    N1, N2 = TREE_EDGE_ABSENT
+    M = TREE_EDGE_M
+    W = lambda kind, prefix: (kind, prefix) + tuple(tree_edge_prefix(prefix))
+    chain = M[0]
+    for i in range(1, 16):                    # 16 terms + 15 AND_MAYBE + 9 SCALE = 40 ops: the longest program
+        chain = ("AND_MAYBE", chain, ("SCALE", 1.0 + i / 8.0, M[i]) if i <= 9 else M[i])
+    cases = [
+        # -- equal estimates: MultiAnd's partial_sort_copy and the OR heap among leaves of one df, every which way
+        ("tie_and_abcd", ("AND", A, B, C, D)), ("tie_and_dcba", ("AND", D, C, B, A)), ("tie_and_bdac", ("AND", B, D, A, C)),
+        ("tie_and_cab", ("AND", C, A, B)),
+        ("tie_or_abcd", ("OR", A, B, C, D)), ("tie_or_dcba", ("OR", D, C, B, A)), ("tie_or_cadb", ("OR", C, A, D, B)),
+        ("tie_or_with_others", ("OR", A, "o10", B, "o05", C, D, "o14")),
+        ("tie_and_with_others", ("AND", "o22", A, "o23", B, "all", C)),
+        ("tie_and_syn_leaf", ("AND", ("SYN", S1, S2), L)), ("tie_and_leaf_syn", ("AND", L, ("SYN", S2, S1))),
+        ("tie_or_syn_leaf", ("OR", ("SYN", S1, S2), L, A)), ("tie_or_leaf_syn", ("OR", A, L, ("SYN", S1, S2))),
+        ("tie_and_leaf_or", ("AND", O, ("OR", A, B))), ("tie_and_or_leaf", ("AND", ("OR", B, A), O)),
+        ("tie_or_scaled", ("OR", ("SCALE", 2.0, A), B, ("SCALE", 0.5, C), (D, 3))),
+        ("tie_maybe_right", ("AND_MAYBE", "o20", A, B, C, D)), ("tie_andnot_right", ("AND_NOT", "all", C, A, B)),
+        # -- the root is a group: tree_len == 0
+        ("root_term", "o12"), ("root_term_wqf", ("o12", 3)), ("root_scale", ("SCALE", 2.5, "o12")), ("root_scale_scale", ("SCALE", 2.0, ("SCALE", 0.25, A))),
+        ("root_syn", ("SYN", A, B)), ("root_syn_of_one", ("SYN", ("o12", 2))),
+        # -- AND / OR of one child is that child
+        ("one_and", ("AND", "o12")), ("one_or_of_and", ("OR", ("AND", A, B))), ("one_and_of_or_of_one", ("AND", ("OR", "o05"))),
+        ("one_inside", ("AND", ("OR", ("AND", "o20")), ("AND", ("OR", "o21", "o19")))),
+        # -- flattening
+        ("flat_filter_in_and", ("AND", A, ("FILTER", B, C))), ("flat_filters_in_and", ("AND", ("FILTER", "o23", "o21"), "o22", ("FILTER", "all", "o20"))),
+        ("flat_filter_of_filter_left", ("FILTER", ("FILTER", A, B), C)), ("flat_filter_of_filter_right", ("FILTER", A, ("FILTER", B, C))),
+        ("flat_or_scale_in_or", ("OR", A, ("SCALE", 2.0, ("OR", B, C)), D)), ("flat_or_scale_in_or_2", ("OR", "o08", ("SCALE", 0.5, ("OR", "o09", "o10")), "o07")),
+        ("flat_maybe_zero_in_filter", ("FILTER", A, ("AND_MAYBE", B, C))), ("flat_maybe_zero_in_andnot", ("AND_NOT", "o20", ("AND_MAYBE", A, B))),
+        ("flat_maybe_zero_deep", ("AND", "o20", ("FILTER", "o19", ("AND_MAYBE", "o18", "o03", "o04")))),
+        # -- AND_NOT / AND_MAYBE with several right-hand children
+        ("sided_andnot_or_and", ("AND_NOT", "o22", "o10", ("OR", "o11", "o12"), ("AND", "o20", "o21"))),
+        ("sided_maybe_or_and", ("AND_MAYBE", "o20", "o10", ("OR", A, B), ("AND", "o21", "o22"))),
+        ("sided_andnot_of_andnot", ("AND_NOT", ("AND_NOT", "o23", "o20"), "o21")), ("sided_andnot_under_andnot", ("AND_NOT", "o23", ("AND_NOT", "o20", "o21"))),
+        ("sided_andnot_many", ("AND_NOT", "all", "o18", "o19", ("OR", "o16", ("OR", "o17", "o15")))),
+        # -- absent terms, at every position
+        ("absent_root", N1), ("absent_and", ("AND", A, N1)), ("absent_or", ("OR", A, N1, B)), ("absent_or_all", ("OR", N1, N2)),
+        ("absent_syn", ("SYN", A, N1)), ("absent_syn_all", ("SYN", N1, N2)), ("absent_syn_in_and", ("AND", ("SYN", N1, "o20"), "o21")),
+        ("absent_andnot_right", ("AND_NOT", A, N1)), ("absent_andnot_left", ("AND_NOT", N1, A)),
+        ("absent_maybe_right", ("AND_MAYBE", A, N1)), ("absent_maybe_left", ("AND_MAYBE", N1, A)),
+        ("absent_filter_right", ("FILTER", A, N1)), ("absent_filter_left", ("FILTER", N1, A)),
+        ("absent_deep", ("OR", ("AND", N1, "o20"), ("AND_MAYBE", "o12", N2), "o03")),
+        # (a WEIGHTED synonym none of whose members the shard holds is no postlist at all, LocalSubMatch::make_synonym_postlist: an OR drops it —
+        #  another Huffman tree, another max_possible —, an AND with it is nothing and lowers no further subquery: total_subqs, the percentages.
+        #  The group comes LAST in lowering order in each of these: see tree_edge_unpinned_cases)
+        ("absent_syn_all_in_or", ("OR", A, B, C, ("SYN", N1, N2))), ("absent_syn_all_scaled", ("OR", A, "o12", ("SCALE", 2.0, ("SYN", N2, N1)))),
+        ("absent_syn_all_in_and_in_or", ("OR", "o12", ("AND", "o22", ("SYN", N1, N2), "o20", "o21"))),
+        ("absent_syn_all_maybe_right", ("AND_MAYBE", A, ("SYN", N1, N2))), ("absent_syn_all_maybe_left", ("OR", "o12", ("AND_MAYBE", ("SYN", N1, N2), "o20"))),
+        ("absent_syn_all_filter_right", ("FILTER", A, ("SYN", N1, N2))), ("absent_syn_all_filter_left", ("OR", "o12", ("FILTER", ("SYN", N1, N2), "o20"))),
+        ("absent_syn_all_andnot_right", ("AND_NOT", A, ("SYN", N1, N2))), ("absent_syn_all_andnot_left", ("OR", "o12", ("AND_NOT", ("SYN", N1, N2), "o20"))),
+        # -- a term in every document: est == db_size, AND_NOT's estimate 0
+        ("all_and", ("AND", "all", A)), ("all_andnot_right", ("AND_NOT", A, "all")), ("all_andnot_left", ("AND_NOT", "all", A)),
+        ("all_or", ("OR", "all", "one")), ("all_maybe", ("AND_MAYBE", "all", "first", "last")),
+        ("all_zero_estimates_tie", ("AND", ("AND_NOT", A, "all"), N1, B)), ("all_filter", ("FILTER", "o05", "all")),
+        # -- synonym groups at the wdf tables' width
+        ("width_syn_508", ("SYN", "w254a", "w254b")), ("width_syn_508_in_or", ("OR", ("SYN", "w254a", "w254b"), "one", "first", "last")),
+        ("width_syn_508_in_and", ("AND", ("SYN", "w254b", "w254a"), "one")), ("width_syn_255", ("SYN", "w254a", "w255")),
+        ("width_syn_808", ("SYN", "w254a", "w254b", "w300")), ("width_or_wide_syn", ("OR", ("SYN", "w255", "w300"), A)),
+        # -- the size limits
+        ("limit_and16", ("AND",) + tuple(M)), ("limit_or16", ("OR",) + tuple(M)),
+        ("limit_and_syn8", ("AND",) + tuple(("SYN", M[2 * i], M[2 * i + 1]) for i in range(8))),
+        ("limit_or_syn8", ("OR",) + tuple(("SYN", M[2 * i + 1], M[2 * i]) for i in range(8))),
+        ("limit_prog40", chain),
+        # -- OP_WILDCARD over the crafted prefixes
+        ("wild_root_eq", W("WILD", "eq")), ("wild_or_root_eq", W("WILD_OR", "eq")), ("wild_m", W("WILD", "m")), ("wild_or_m", W("WILD_OR", "m")),
+        ("wild_w25_in_and", ("AND", W("WILD", "w25"), "all")), ("wild_or_in_or", ("OR", A, W("WILD_OR", "w25"), "o10")),
+        ("wild_of_one", W("WILD", "fir")), ("wild_or_of_one", ("AND_MAYBE", "all", W("WILD_OR", "las"))),
+        # -- an OR over AND_NOT / AND_MAYBE children
+        ("quirk_or_sided", ("OR", ("AND_NOT", A, B), ("AND_MAYBE", C, D), ("o12", 2))), ("quirk_or_andnot", ("OR", ("AND_NOT", "o20", "o21"), "o05")),
+        ("quirk_or_maybe", ("OR", ("AND_MAYBE", "o10", "o22"), ("AND_MAYBE", "o11", "o23"))),
+    ]
+    assert len({n for n, _ in cases}) == len(cases)
+    assert len(tree_program(chain)[2]) == 40
+    return cases
+
+
+def tree_edge_unpinned_cases():
+    """[(name, tree)]: an all-absent weighted synonym group with a term lowered AFTER it.  The compiled reference cannot pin these: it deletes the
+    group's OR together with the leaf postlist its optimiser keeps as a hint (localsubmatch.cc:205-209, 273-279) and opens the next term through the
+    dangling pointer — it crashes.  The oracle and the device lower them by the rule the reference's code states; they are compared with each other."""
+    A, B, C = "eqA", "eqB", "eqC"
+    N1, N2 = TREE_EDGE_ABSENT
+    return [("unpinned_syn_all_first_in_or", ("OR", ("SYN", N1, N2), A, B, C)), ("unpinned_syn_all_scaled", ("OR", A, ("SCALE", 2.0, ("SYN", N2, N1)), "o12")),
+            ("unpinned_syn_all_in_and_in_or", ("OR", ("AND", "o22", ("SYN", N1, N2), "o20", "o21"), "o12")),
+            ("unpinned_syn_all_maybe_left", ("OR", ("AND_MAYBE", ("SYN", N1, N2), "o20"), "o12"))]
+
+
+def tree_has_or_over_sided(tree):
+    """Whether a tree holds an OR with an AND_NOT / AND_MAYBE child — the only shape that may be flagged as the reference's quirk."""
+    if isinstance(tree, str) or tree[0] not in T_KIND:
+        return False
+    kids = [k for k in (tree[2:] if tree[0] in _WILD + ("SCALE",) else tree[1:]) if not isinstance(k, str)]
+    if tree[0] == "OR" and any(k[0] in ("AND_NOT", "AND_MAYBE") for k in kids):
+        return True
+    return any(tree_has_or_over_sided(k) for k in kids)
+
+
+def tree_edge_queries(cases=None, first=0, maxitems=10):
+    return [dict(op="RPN", name=n, tree=t, terms=tree_rpn(t), first=first, maxitems=maxitems, window=0) for n, t in (cases or tree_edge_cases())]
+
+
+def tree_edge_declined():
+    """[dict(name, terms, ops, want, n_terms, n_tree)]: programs xgm_plan_query must refuse, with the outcome plan_tree gives each: "UNSUPPORTED"
+    (a shape the device does not take: the CPU matcher's) or "INVALID" (a program no Query builds).  ops = [(kind, arity, term, scale)] as
+    tree_program makes them; n_terms / n_tree, where given, overrule the lengths (17 terms and 41 ops do not fit the descriptor's arrays: the
+    planner refuses by the counts alone)."""
+    K = T_KIND
+    T = lambda i: (K["TERM"], 0, i, 1.0)
+    prog = lambda tree: tree_program(tree)
+    out = []
+
+    def add(name, want, terms, ops, **kw):
+        out.append(dict(name=name, want=want, terms=list(terms), ops=list(ops), n_terms=kw.get("n_terms", len(terms)), n_tree=kw.get("n_tree", len(ops))))
+    t16, _, o16 = prog(("AND",) + tuple(TREE_EDGE_M))
+    add("terms_17", "UNSUPPORTED", t16, o16, n_terms=17)
+    chain = dict(tree_edge_cases())["limit_prog40"]
+    t40, _, o40 = prog(chain)
+    add("ops_41", "UNSUPPORTED", t40, o40, n_tree=41)
+    add("ops_0", "UNSUPPORTED", ["eqA"], [], n_tree=0)
+    for name, f in (("scale_zero", 0.0), ("scale_negative", -1.5), ("scale_nan", float("nan"))):
+        add(name, "UNSUPPORTED", ["eqA"], [T(0), (K["SCALE"], 1, 0, f)])
+    add("term_index_twice", "UNSUPPORTED", ["eqA", "eqB"], [T(0), T(0), (K["AND"], 2, 0, 1.0)])
+    add("term_bytes_twice", "UNSUPPORTED", ["eqA", "eqA"], [T(0), T(1), (K["OR"], 2, 0, 1.0)])
+    add("term_index_out_of_range", "UNSUPPORTED", ["eqA", "eqB"], [T(0), T(2), (K["AND"], 2, 0, 1.0)])
+    add("term_unused", "UNSUPPORTED", ["eqA", "eqB", "eqC"], [T(0), T(1), (K["AND"], 2, 0, 1.0)])
+    add("syn_over_and", "UNSUPPORTED", ["eqA", "eqB", "eqC"], [T(0), T(1), (K["AND"], 2, 0, 1.0), T(2), (K["SYN"], 2, 0, 1.0)])
+    add("wild_over_scale", "UNSUPPORTED", ["eqA", "eqB"], [T(0), (K["SCALE"], 1, 0, 2.0), T(1), (K["WILD"], 2, 0, 1.0)])
+    add("wild_or_over_or", "UNSUPPORTED", ["eqA", "eqB", "eqC"], [T(0), T(1), (K["OR"], 2, 0, 1.0), T(2), (K["WILD_OR"], 2, 0, 1.0)])
+    add("arity_0", "INVALID", ["eqA"], [T(0), (K["AND"], 0, 0, 1.0)])
+    add("arity_beyond_stack", "INVALID", ["eqA", "eqB"], [T(0), T(1), (K["OR"], 3, 0, 1.0)])
+    add("operator_first", "INVALID", ["eqA"], [(K["SCALE"], 1, 0, 2.0), T(0)])
+    add("filter_of_3", "INVALID", ["eqA", "eqB", "eqC"], [T(0), T(1), T(2), (K["FILTER"], 3, 0, 1.0)])
+    add("filter_of_1", "INVALID", ["eqA"], [T(0), (K["FILTER"], 1, 0, 1.0)])
+    add("andnot_of_1", "INVALID", ["eqA"], [T(0), (K["AND_NOT"], 1, 0, 1.0)])
+    add("maybe_of_1", "INVALID", ["eqA"], [T(0), (K["AND_MAYBE"], 1, 0, 1.0)])
+    add("two_roots", "INVALID", ["eqA", "eqB"], [T(0), T(1)])
+    add("unknown_kind", "INVALID", ["eqA", "eqB"], [T(0), T(1), (10, 2, 0, 1.0)])
+    return out

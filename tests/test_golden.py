@@ -19,6 +19,12 @@ def shards_for(fx):
         if key not in _cache:
             _cache[key] = [H.ManualCorpus(*H.coloc_postings(fx["coloc"]["seed"], fx["coloc"]["n_docs"]))]
         return _cache[key]
+    if "tree_edges" in fx:                 # the crafted corpus of the nested-query edges (helpers.tree_edge_postings), deleted documents and all
+        key = ("tree_edges", fx["tree_edges"]["lastdocid"])
+        if key not in _cache:
+            assert fx["tree_edges"]["lastdocid"] == H.TREE_EDGE_LASTDOCID
+            _cache[key] = [H.ManualCorpus(*H.tree_edge_postings())]
+        return _cache[key]
     c = fx["corpus"]
     key = (c["seed"], c["n_docs"], c["vocab"], fx["n_shards"])
     if key not in _cache:
@@ -31,6 +37,12 @@ def expected(r):
     return [(d, float.fromhex(w)) for d, w, _ in r["hits"]]
 
 
+def hits_digest(rows, pct):
+    """tests/golden/make_golden.py::hits_digest over the oracle's rows: a long page is recorded as its length and this."""
+    import hashlib
+    return hashlib.sha256("".join("%d %s %d\n" % (d, w.hex(), p) for (d, w, _), p in zip(rows, pct)).encode()).hexdigest()
+
+
 @pytest.mark.parametrize("path", GOLDEN, ids=[os.path.basename(p) for p in GOLDEN])
 def test_oracle_matches_golden(path):
     fx = json.load(open(path))
@@ -39,9 +51,18 @@ def test_oracle_matches_golden(path):
     for r in fx["results"]:
         q = r["query"]
         if q["op"] == "RPN":
-            rows, hdr, _ = H.oracle_search_tree(shards[0], H.tree_from_json(q["tree"]), q["first"], q["maxitems"])
-            got = [(d, w) for d, w, _ in rows[q["first"]:]]
-            assert hdr.max_possible == float.fromhex(r["max_possible"])
+            rows, hdr, total_subqs = H.oracle_search_tree(shards[0], H.tree_from_json(q["tree"]), q["first"], q["maxitems"])
+            page = rows[q["first"]:]
+            got = [(d, w) for d, w, _ in page]
+            assert hdr.max_possible == float.fromhex(r["max_possible"]), q
+            # the best weight of the whole match and the percentages: matched / total weighted subqueries of the best document
+            pct = H.tree_percentages(page, hdr, total_subqs) if rows else []
+            if rows:
+                assert hdr.max_attained == float.fromhex(r["max_attained"]), q
+            if "hits" not in r:                # a long page: its length and digest
+                assert (len(page), hits_digest(page, pct)) == (r["n_hits"], r["hits_sha256"]), q
+                continue
+            assert pct == [p for _, _, p in r["hits"]], q
         elif q.get("spy") is not None:
             total, counts = H.oracle_spy(shards[0], q["op"], q["terms"], q["spy"], n_required=q.get("n_required", 0))
             assert (total, [[v.hex(), n] for v, n in counts]) == (r["spy_total"], r["spy"]), q

@@ -218,3 +218,61 @@ def test_prefix_expansion_walks_the_dictionary_in_term_order(host_env):
             assert tf.value == tf_of[t], (t, tf.value, tf_of[t])
         assert got == want[:len(got)], (prefix, got[:5], want[:5])
         assert list(small[:min(5, len(want))]) == list(ids[:min(5, len(want))])
+
+
+# ---- nested queries at the planner's limits (helpers.tree_edge_declined / tree_edge_cases) ----------------------------------------------
+
+@pytest.fixture(scope="module")
+def edge_db(built, tmp_path_factory):
+    c = H.ManualCorpus(*H.tree_edge_postings())
+    db = Database(c.build_segment(str(tmp_path_factory.mktemp("edges") / "e.seg")), device=_lib.XGM_DEVICE_NONE)
+    yield db
+    db.close()
+    c.close()
+
+
+def raw_tree_plan(db, terms, ops, n_terms=None, n_tree=None):
+    """xgm_plan_query on a descriptor filled by hand — counts beyond the arrays included, which enquire.plan would refuse itself.  Returns (rc, plan)."""
+    import ctypes as C
+    d = _lib.QueryDesc()
+    d.op = _lib.XGM_OP_TREE
+    for i, t in enumerate(terms[:_lib.XGM_MAX_TERMS]):
+        d.terms[i], d.term_len[i], d.wqf[i] = t.encode(), len(t), 1
+    for i, (kind, arity, term, scale) in enumerate(ops[:_lib.XGM_MAX_TREE]):
+        d.tree[i].kind, d.tree[i].arity, d.tree[i].term = kind, arity, term
+        d.tree_scale[i] = scale
+    d.n_terms = len(terms) if n_terms is None else n_terms
+    d.n_tree = len(ops) if n_tree is None else n_tree
+    d.first, d.maxitems = 0, 10
+    w = BM25Weight()
+    d.k1, d.k2, d.k3, d.b, d.min_normlen = w.k1, w.k2, w.k3, w.b, w.min_normlen
+    q = _lib.Query()
+    return _lib.lib().xgm_plan_query(db._h, C.byref(d), None, C.byref(q)), q
+
+
+def test_tree_programs_the_planner_refuses(edge_db):
+    """17 terms, 41 ops, a scale that is not positive, a term twice (by index, by bytes), a group over a non-term: XGM_UNSUPPORTED — the CPU
+    matcher's; arities no Query has, a stack that does not end on one value, an unknown node kind: XGM_E_INVALID."""
+    want = {"UNSUPPORTED": _lib.XGM_UNSUPPORTED, "INVALID": _lib.XGM_E_INVALID}
+    declined = H.tree_edge_declined()
+    assert {e["want"] for e in declined} == set(want) and len(declined) >= 20
+    for e in declined:
+        rc, _ = raw_tree_plan(edge_db, e["terms"], e["ops"], e["n_terms"], e["n_tree"])
+        assert rc == want[e["want"]], (e["name"], rc)
+    # ... and each of them for its stated reason alone: the same programs without the flaw are planned
+    assert raw_tree_plan(edge_db, ["eqA", "eqB"], [(0, 0, 0, 1.0), (0, 0, 1, 1.0), (H.T_KIND["AND"], 2, 0, 1.0)])[0] == _lib.XGM_OK
+    assert raw_tree_plan(edge_db, ["eqA"], [(0, 0, 0, 1.0), (H.T_KIND["SCALE"], 1, 0, 1e-300)])[0] == _lib.XGM_OK
+
+
+def test_the_longest_tree_program_is_planned(edge_db):
+    """XGM_MAX_TREE = 40 ops over XGM_MAX_TERMS = 16 terms: accepted, sixteen groups and fifteen nodes; one op more is refused."""
+    tree = dict(H.tree_edge_cases())["limit_prog40"]
+    terms, _, ops = H.tree_program(tree)
+    assert len(ops) == _lib.XGM_MAX_TREE and len(terms) == _lib.XGM_MAX_TERMS
+    rc, q = raw_tree_plan(edge_db, terms, ops)
+    assert rc == _lib.XGM_OK and q.n_groups == 16 and q.tree_len == 15 and q.total_subqs == 16
+    p = plan(edge_db, Query.tree(tree), 0, 10)
+    assert (p.n_groups, p.tree_len, p.tree_root, p.max_possible) == (q.n_groups, q.tree_len, q.tree_root, q.max_possible)
+    assert raw_tree_plan(edge_db, terms, ops, n_tree=_lib.XGM_MAX_TREE + 1)[0] == _lib.XGM_UNSUPPORTED
+    with pytest.raises(_lib.XgmUnsupported):
+        plan(edge_db, Query.tree(("SCALE", 2.0, tree)), 0, 10)

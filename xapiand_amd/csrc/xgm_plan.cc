@@ -223,6 +223,7 @@ struct TreePlanner {
     uint32_t N = 0, db_size = 0; double len_factor = 0;
     uint32_t local_id[XGM_MAX_TERMS], tf_local[XGM_MAX_TERMS], tf_global[XGM_MAX_TERMS];
     bool used[XGM_MAX_TERMS] = {};
+    bool grouped[XGM_MAX_TERMS] = {};          /* the term stands in a group: its subquery was lowered to a postlist */
     int rc = XGM_OK;
 
     int add(PNode&& n) { pl.push_back(std::move(n)); return (int)pl.size() - 1; }
@@ -239,7 +240,7 @@ struct TreePlanner {
         const double w = bm25_termweight(N, tf_global[t], d->k1, d->k3, d->wqf[t] ? d->wqf[t] : 1u, factor);
         const uint32_t wdf_ub = local_id[t] == UINT32_MAX ? 0u : idx->term_wdfub[local_id[t]];
         const int x = new_group(weighted ? w : 0.0, weighted, weighted ? bm25_maxpart(w, len_factor, d->k1, d->b, d->min_normlen, wdf_ub, idx->hdr.doclen_lower_bound) : 0.0, tf_local[t]);
-        if (x >= 0) out->group_of[t] = (uint8_t)pl[x].group;
+        if (x >= 0) { out->group_of[t] = (uint8_t)pl[x].group; grouped[t] = true; }
         return x;
     }
     int synonym(const std::vector<int>& terms, double factor) {
@@ -257,12 +258,20 @@ struct TreePlanner {
             for (size_t i = 1; i < terms.size(); ++i) { const double Pi = tf_global[terms[i]] * scale; P += Pi - P * Pi; }
             tf_syn = (uint32_t)(P * N + 0.5);
         }
+        /* LocalSubMatch::make_synonym_postlist, localsubmatch.cc:205-209: a WEIGHTED synonym none of whose members the shard holds
+         * (or_pl->get_termfreq_max() == 0) is NO postlist — QuerySynonym::postlist has counted it as a subquery all the same; an
+         * unweighted one is its BoolOrPostList (do_synonym, queryinternal.cc:1827-1832) and stays */
+        if (weighted) {
+            bool any = false;
+            for (int t : terms) any = any || tf_local[t] != 0;
+            if (!any) { ++out->total_subqs; return -1; }
+        }
         const double w = bm25_termweight(N, tf_syn, d->k1, d->k3, 1u, factor);
         /* Weight::init_ (synonym case, weight.cc:86-115): the wdf bound of a synonym is the doclength upper bound */
         const int x = new_group(weighted ? w : 0.0, weighted,
                                 weighted ? bm25_maxpart(w, len_factor, d->k1, d->b, d->min_normlen, idx->hdr.doclen_upper_bound, idx->hdr.doclen_lower_bound) : 0.0, est);
         if (x >= 0) {
-            for (int t : terms) out->group_of[t] = (uint8_t)pl[x].group;
+            for (int t : terms) { out->group_of[t] = (uint8_t)pl[x].group; grouped[t] = true; }
             std::vector<Est> k;
             for (int t : terms) k.push_back(est_leaf(tf_local[t]));
             pl[x].e = est_boolor(k, db_size);
@@ -310,16 +319,24 @@ struct TreePlanner {
             heap_sift_down(heap, heap.size(), 0);
         }
     }
-    void sub_and_like(int a, std::vector<int>& ctx, double factor) {
+    /* postlist() returns -1 with rc == XGM_OK where the reference has a NULL postlist (above).  AndContext::add_postlist then empties the
+     * context and the lowering of the AND stops — the subqueries after it are never lowered, nor counted (queryinternal.cc:564-571,
+     * 2092-2103); an OR context skips it (:198-201); AND_NOT / AND_MAYBE / FILTER are nothing without their left side, which is lowered
+     * first, and are their left side without the right (:2208-2283). */
+    bool sub_and_like(int a, std::vector<int>& ctx, double factor) {
         const ANode& n = ast[a];
-        if (n.kind == XGM_T_AND) { for (int k : n.kids) sub_and_like(k, ctx, factor); return; }
-        if (n.kind == XGM_T_FILTER) { for (int k : n.kids) { sub_and_like(k, ctx, factor); factor = 0.0; } return; }
-        ctx.push_back(postlist(a, factor));
+        if (n.kind == XGM_T_AND) { for (int k : n.kids) if (!sub_and_like(k, ctx, factor)) return false; return true; }
+        if (n.kind == XGM_T_FILTER) { for (int k : n.kids) { if (!sub_and_like(k, ctx, factor)) return false; factor = 0.0; } return true; }
+        const int x = postlist(a, factor);
+        if (x < 0) { ctx.clear(); return false; }
+        ctx.push_back(x);
+        return true;
     }
     void sub_or_like(int a, std::vector<int>& ctx, double factor) {
         const ANode& n = ast[a];
         if (n.kind == XGM_T_OR) { for (int k : n.kids) sub_or_like(k, ctx, factor); return; }
-        ctx.push_back(postlist(a, factor));
+        const int x = postlist(a, factor);
+        if (x >= 0) ctx.push_back(x);
     }
     int postlist(int a, double factor) {
         if (rc) return -1;
@@ -327,15 +344,22 @@ struct TreePlanner {
         switch (n.kind) {
         case XGM_T_TERM: return leaf(n.term, factor);
         case XGM_T_SCALE: return postlist(n.kids[0], factor * n.scale);
-        case XGM_T_AND: { std::vector<int> ctx; sub_and_like(a, ctx, factor); return rc ? -1 : mand(ctx); }
-        case XGM_T_FILTER: { const int l = postlist(n.kids[0], factor); const int r = postlist(n.kids[1], 0.0); return rc ? -1 : mand({l, r}); }
+        case XGM_T_AND: { std::vector<int> ctx; const bool some = sub_and_like(a, ctx, factor); return rc || !some ? -1 : mand(ctx); }
+        case XGM_T_FILTER: {
+            const int l = postlist(n.kids[0], factor);
+            if (l < 0) return -1;
+            const int r = postlist(n.kids[1], 0.0);
+            return rc || r < 0 ? -1 : mand({l, r});
+        }
         case XGM_T_OR: { std::vector<int> ctx; sub_or_like(a, ctx, factor); return rc ? -1 : or_tree(ctx); }
         case XGM_T_AND_NOT: {
             const int l = postlist(n.kids[0], factor);
+            if (l < 0) return -1;
             std::vector<int> ctx;
             for (size_t i = 1; i < n.kids.size(); ++i) sub_or_like(n.kids[i], ctx, 0.0);
             if (rc) return -1;
             const int r = or_tree(ctx);
+            if (r < 0) return l;
             PNode p; p.type = P_ANDNOT; p.kids = {l, r};
             double e = pl[l].est;
             e = (e * (db_size - (double)pl[r].est)) / db_size;
@@ -346,11 +370,12 @@ struct TreePlanner {
         }
         case XGM_T_AND_MAYBE: {
             const int l = postlist(n.kids[0], factor);
-            if (factor == 0.0) return l;
+            if (l < 0 || factor == 0.0) return l;
             std::vector<int> ctx;
             for (size_t i = 1; i < n.kids.size(); ++i) sub_or_like(n.kids[i], ctx, factor);
             if (rc) return -1;
             const int r = or_tree(ctx);
+            if (r < 0) return l;
             PNode p; p.type = P_MAYBE; p.kids = {l, r}; p.est = pl[l].est; p.maxw = pl[l].maxw + pl[r].maxw; p.e = pl[l].e;
             return add(std::move(p));
         }
@@ -446,6 +471,24 @@ int plan_tree(const xgm_index* idx, const xgm_query_desc* d, const xgm_global_st
     out->n_terms = n;
     const int root = tp.postlist(stack[0], 1.0);
     if (tp.rc) return tp.rc;
+    /* the terms of subqueries that were never lowered, or whose synonym is no postlist: one group of their own that no node reads */
+    {
+        int dead = -1;
+        for (uint32_t i = 0; i < n; ++i) {
+            if (tp.grouped[i]) continue;
+            if (dead < 0) { const int x = tp.new_group(0.0, false, 0.0, 0u); if (x < 0) return tp.rc; dead = tp.pl[x].group; }
+            out->group_of[i] = (uint8_t)dead;
+        }
+    }
+    if (root < 0) {
+        /* no postlist at all: the empty MSet, max_possible 0 — a node no document satisfies */
+        out->tree_len = 1; out->tree_op[0] = XGM_N_ANDNOT; out->tree_a[0] = out->tree_b[0] = 0;
+        out->tree_root = (uint8_t)out->n_groups;
+        out->max_possible = 0.0;
+        out->est_min = out->est_est = out->est_max = 0;
+        for (uint32_t i = 0; i < n; ++i) out->terms[i].termweight = out->group_weight[out->group_of[i]];
+        return XGM_OK;
+    }
     const int dev_root = tp.emit(root);
     if (tp.rc) return tp.rc;
     /* renumber the provisional node ids now that the number of groups is known */

@@ -74,12 +74,16 @@ class Query:
             self.n_required = n_required
 
     # -- nested queries ---------------------------------------------------------------------------------------------
-    _T = {"AND": 1, "OR": 2, "AND_NOT": 3, "AND_MAYBE": 4, "FILTER": 5, "SYN": 6, "SYNONYM": 6, "SCALE": 7}
+    _T = {"AND": 1, "OR": 2, "AND_NOT": 3, "AND_MAYBE": 4, "FILTER": 5, "SYN": 6, "SYNONYM": 6, "SCALE": 7,
+          "WILD": 8, "WILDCARD": 8, "WILD_OR": 9, "WILDCARD_OR": 9}          # include/xgm.h: XGM_T_WILDCARD, XGM_T_WILDCARD_OR
+    _WILD = ("WILD", "WILDCARD", "WILD_OR", "WILDCARD_OR")
 
     @classmethod
     def tree(cls, spec):
         """A nested query from tuples: "term" | ("term", wqf) | ("AND", q, q, ...) | ("OR", ...) | ("SYNONYM", term, ...) |
-        ("AND_NOT", left, right...) | ("AND_MAYBE", left, right...) | ("FILTER", left, right) | ("SCALE", factor, q) —
+        ("AND_NOT", left, right...) | ("AND_MAYBE", left, right...) | ("FILTER", left, right) | ("SCALE", factor, q) |
+        ("WILDCARD", prefix, term, ...) | ("WILDCARD_OR", prefix, term, ...) — an OP_WILDCARD "prefix*" with the OP_SYNONYM /
+        OP_OR combiner over its expansion, which the caller lists in term order (xgm_expand_prefix) —
         the Xapian::Query trees Xapiand's DSL builds (reference src/query_dsl.cc:188-432), lowered by xgm_plan_query like
         src/xapian/api/queryinternal.cc does."""
         q = cls.__new__(cls)
@@ -96,9 +100,10 @@ class Query:
                 walk(t[2])
                 q.ops.append((7, 1, 0, float(t[1])))
                 return
-            for k in t[1:]:
+            kids = t[2:] if t[0] in cls._WILD else t[1:]              # (a wildcard's first item is its prefix)
+            for k in kids:
                 walk(k)
-            q.ops.append((cls._T[t[0]], len(t) - 1, 0, 1.0))
+            q.ops.append((cls._T[t[0]], len(kids), 0, 1.0))
         walk(spec)
         return q
 
