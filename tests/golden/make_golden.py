@@ -11,6 +11,8 @@ other fixtures cover OR-5 top-100, full-result PHRASE, paging (first > 0), the t
 next widening row — the value sorts (sort keys recorded) and a ValueCountMatchSpy's counts over the whole match.
 tree_edges.json: the nested queries of helpers.tree_edge_cases() on the crafted corpus of helpers.tree_edge_postings(), a top-10 page and the
 whole match of each (`python tests/golden/make_golden.py tree_edges` writes that fixture alone).
+positional_edges.json: the PHRASE / NEAR cases of helpers.positional_edge_cases() on the crafted corpus of helpers.positional_edge_postings(), the whole match
+of each (`python tests/golden/make_golden.py positional_edges` writes that fixture alone).
 """
 import json
 import os
@@ -88,6 +90,36 @@ def tree_edges(tmp):
     print("tree_edges: %d cases, flagged as reference quirks: %s" % (len(cases), flagged))
 
 
+def positional_edges(tmp):
+    """The crafted positional cases through the compiled reference: the whole match of every case (maxitems covers the conjunction, so neither the
+    stale SelectPostList weight nor NEAR's history can engage: positions inside a document are distinct).  A case the reference itself crashes on
+    would be recorded without an answer and named; at most three may."""
+    import subprocess
+    post, doclen = H.positional_edge_postings()
+    pf, db = os.path.join(tmp, "pos.txt"), os.path.join(tmp, "dbp")
+    H.write_postings_file(pf, post, doclen)
+    H.xapian_ref("build_postings", db, pf)
+    cases = H.positional_edge_cases()
+    try:
+        results, crashed = run(tmp, [db], cases, "posedges"), []
+    except subprocess.CalledProcessError:                          # one by one: which case takes the reference down
+        results, crashed = [], []
+        for c in cases:
+            try:
+                results += run(tmp, [db], [c], "posedge1")
+            except subprocess.CalledProcessError:
+                crashed.append(c["name"])
+                results.append(dict(query=c, reference_crashed=True))
+    assert len(crashed) <= 3, crashed
+    for r in results:
+        if len(r.get("hits", ())) > LONG_PAGE:
+            r["n_hits"], r["hits_sha256"] = len(r["hits"]), hits_digest(r["hits"])
+            del r["hits"]
+    with open(os.path.join(HERE, "positional_edges.json"), "w") as f:
+        json.dump(dict(positional_edges=dict(lastdocid=H.POS_EDGE_LASTDOCID, seed=H.POS_EDGE_SEED), n_shards=1, results=results), f, indent=0)
+    print("positional_edges: %d cases, the reference crashed on: %s" % (len(cases), crashed))
+
+
 def sharded(tmp, corpus, n_shards):
     """Xapiand's per-shard protocol (prepare_mset / add_prepared_mset / get_mset per shard / unshard_docids + merge_mset, handler.cc:1532-1549)
     over n_shards docid-interleaved shards (multi.h:38-73) through the compiled reference: 4 shards (rounds 1-4) and — C4's shape, the
@@ -111,6 +143,10 @@ def main():
     if sys.argv[1:] == ["tree_edges"]:
         with tempfile.TemporaryDirectory() as tmp:
             tree_edges(tmp)
+        return
+    if sys.argv[1:] == ["positional_edges"]:
+        with tempfile.TemporaryDirectory() as tmp:
+            positional_edges(tmp)
         return
     with tempfile.TemporaryDirectory() as tmp:
         db = os.path.join(tmp, "db")
@@ -158,6 +194,7 @@ def main():
         with open(os.path.join(HERE, "near_colocated.json"), "w") as f:
             json.dump(dict(coloc=dict(seed=0xC010C, n_docs=600), n_shards=1, results=run(tmp, [dbc], H.coloc_near_queries(), "coloc")), f, indent=0)
         tree_edges(tmp)
+        positional_edges(tmp)
         sharded(tmp, corpus, 4)
         sharded(tmp, corpus, 8)
     print("golden fixtures written to", HERE)

@@ -1072,3 +1072,449 @@ def tree_edge_declined():
     add("two_roots", "INVALID", ["eqA", "eqB"], [T(0), T(1)])
     add("unknown_kind", "INVALID", ["eqA", "eqB"], [T(0), T(1), (10, 2, 0, 1.0)])
     return out
+
+
+# ---- the positional filter (PHRASE, windowed PHRASE, NEAR) at its edges: a crafted corpus, an explicit table of cases ----
+#
+# The corpus is made of GROUPS.  A group is a run of at most 64 consecutive docids inside one stripe of 256, and a set of terms of its own:
+# every document of the group holds every term of the group, nothing else does — the conjunction of a case IS its group, whatever the
+# positions say.  A term of a "dense" flavour also stands (once, wdf 1) in some 480 - 510 of the filler documents 1 .. 2048, in a residue
+# class of its own, so that it has probe containers (32 postings per stripe on average) while no filler document holds two terms of one
+# group; a rare term has a flat posting array.  How many filler documents a term stands in fixes the plan order (ascending termfreq).
+
+POS_EDGE_LASTDOCID, POS_EDGE_FILL, POS_EDGE_SEED = 3839, 2048, 0x9051ED6E
+POS_EDGE_MAXITEMS, POS_EDGE_MAX_CONJ = 192, 150
+POS_EDGE_FLAVOUR_STEP = 16400            # a group's documents carry the same lists once per flavour, this far apart (four flavours stay 2-byte)
+LEN16 = (1, 4, 5, 8, 9, 16, 17, 32, 33, 48, 49, 64, 65, 128, 254)          # list lengths of a term, 2-byte lists: fast | wide | serial
+LEN32 = (1, 4, 5, 16, 17, 64, 65, 252, 253, 254)                            # ... 4-byte lists
+DECISIVE = (0, 7, 8, 15, 16, 31, 32, 47, 48, 63, 64)                        # where in the long list the deciding position sits (and n - 1)
+
+
+class _Cur:
+    """A PositionList over a sorted list: next / skip_to / get_position, forward only."""
+
+    def __init__(self, pp):
+        self.p, self.c = pp, -1
+
+    def next(self):
+        self.c += 1
+        return self.c < len(self.p)
+
+    def skip_to(self, want):
+        if self.c < 0:
+            self.c = 0
+        while self.c < len(self.p) and self.p[self.c] < want:
+            self.c += 1
+        return self.c < len(self.p)
+
+    def get(self):
+        return self.p[self.c]
+
+
+def py_phrase_exact(lists):
+    """ExactPhrasePostList::test_doc (exactphrasepostlist.cc:75-133) on the lists in PHRASE order."""
+    n = len(lists)
+    order = sorted(range(n), key=lambda i: len(lists[i]))              # by wdf; a stable sort, as std::sort is on so few
+    pl = [_Cur(lists[i]) for i in order]
+    if not pl[0].skip_to(order[0]):
+        return False
+    if len(pl[0].p) > len(pl[1].p):
+        if not pl[1].skip_to(order[1]):
+            return False
+        pl[0], pl[1] = pl[1], pl[0]
+        order[0], order[1] = order[1], order[0]
+    idx0 = order[0]
+    base = pl[0].get() - idx0
+    i = 1
+    while True:
+        required = base + order[i]
+        if not pl[i].skip_to(required):
+            return False
+        got = pl[i].get()
+        if got == required:
+            i += 1
+            if i == n:
+                return True
+            continue
+        if not pl[0].skip_to(got - order[i] + idx0):
+            return False
+        base = pl[0].get() - idx0
+        i = 1
+
+
+def py_phrase_window(lists, window):
+    """PhrasePostList::test_doc (phrasepostlist.cc:60-90) on the lists in PHRASE order."""
+    n = len(lists)
+    pl = [_Cur(pp) for pp in lists]
+    if not pl[0].next():
+        return False
+    while True:
+        base = pos = pl[0].get()
+        i = 0
+        while True:
+            i += 1
+            if i == n:
+                return True
+            if not pl[i].skip_to(pos + 1):
+                return False
+            pos = pl[i].get()
+            b = pos + (n - i)
+            if not b - base <= window:
+                break
+        if not pl[0].skip_to(b - window):
+            return False
+
+
+def py_near(lists, window):
+    """NearPostList::test_doc (nearpostlist.cc:60-160) for lists that share no position: started lazily in ascending wdf order, the smallest
+    head skipped to last - window + 1 while the span is too wide.  The duplicate-position walk (lines 106-140) finds nothing to move."""
+    order = sorted(range(len(lists)), key=lambda i: len(lists[i]))
+    heads = [_Cur(lists[order[0]])]
+    if not heads[0].next():
+        return False
+    last = heads[0].get()
+    while True:
+        top = min(heads, key=lambda c: c.get())
+        if last - top.get() < window:
+            if len(heads) != len(lists):
+                c = _Cur(lists[order[len(heads)]])
+                if last < window:
+                    if not c.next():
+                        return False
+                elif not c.skip_to(last - window + 1):
+                    return False
+                last = max(last, c.get())
+                heads.append(c)
+                continue
+            assert len({c.get() for c in heads}) == len(heads)
+            return True
+        if not top.skip_to(last - window + 1):
+            return False
+        last = max(last, top.get())
+
+
+def py_positional(op, lists, window):
+    """The verdict of the reference's procedures on one document; lists in query order, window 0 = the number of terms."""
+    n = len(lists)
+    w = window or n
+    if op == "NEAR":
+        return py_near(lists, w)
+    return py_phrase_exact(lists) if w == n else py_phrase_window(lists, w)
+
+
+def full_search_positional(op, lists, window):
+    """What the procedures are FOR, by exhaustive search: PHRASE — positions p_0 < p_1 < ... in phrase order with p_i + (n - i) - p_0 <= window
+    for every i >= 1 (window == n: p_i = p_0 + i); NEAR — one position of every term inside a span shorter than the window."""
+    n = len(lists)
+    w = window or n
+    if op == "NEAR":
+        return any(all(any(x <= p < x + w for p in pp) for pp in lists) for x in set().union(*lists))
+    if w == n:
+        sets = [set(pp) for pp in lists]
+        return any(all(b + i in sets[i] for i in range(n)) for b in lists[0])
+
+    def chain(i, prev, base):
+        return i == n or any(chain(i + 1, p, base) for p in lists[i] if p > prev and p + (n - i) - base <= w)
+    return any(chain(1, b, b) for b in lists[0])
+
+
+def _craft_lists(op, window, T, p_long, n, idx, match, stride=64):
+    """T lists in query order: list p_long has n entries `stride` apart, every other list one entry, placed so that entry idx of the long
+    list decides — a match, or (match False) the near-miss: one deciding position moved by one."""
+    w = window or T
+    assert stride > w + T and 0 <= idx < n
+    L = [16 + T + stride * m for m in range(n)]
+    x = L[idx]
+    lists = [None] * T
+    lists[p_long] = L
+    others = [j for j in range(T) if j != p_long]
+    if op == "NEAR":                                  # the others next to x, the last of them at the far end of the window
+        for k, j in enumerate(others[:-1]):
+            lists[j] = [x + 1 + k]
+        lists[others[-1]] = [x + w - 1 + (0 if match else 1)]
+    elif w == T:                                      # exact: word j at base + j; the near-miss moves an outer word outwards
+        for j in others:
+            lists[j] = [x - p_long + j]
+        if not match:
+            q = others[-1] if others[-1] > p_long else others[0]
+            lists[q] = [lists[q][0] + (1 if q > p_long else -1)]
+    else:                                             # windowed: words 0 .. T-2 side by side, the last one window - 1 after the first (or window)
+        far = w - 1 + (0 if match else 1)
+        base = x - (far if p_long == T - 1 else p_long)
+        for j in others:
+            lists[j] = [base + (far if j == T - 1 else j)]
+    return lists
+
+
+class _PosEdgeBuilder:
+    def __init__(self):
+        self.rng = random.Random(POS_EDGE_SEED)
+        self.post, self.doclen, self.next_doc = {}, {}, POS_EDGE_FILL + 1
+        self.fill_pos = {}
+        self.cases, self.intent, self.term_info, self.groups = [], {}, {}, {}
+
+    def _put(self, term, d, pp):
+        pp = sorted(pp)
+        assert len(set(pp)) == len(pp) and pp
+        self.post.setdefault(term, []).append((d, len(pp), pp))
+        self.doclen[d] = self.doclen.get(d, 0) + len(pp)
+
+    def term(self, name, j, extras, wide=False):
+        """A term standing `extras` times in the filler documents of residue class j % 4 (rare terms of long queries: their own stretch of it)."""
+        cls = [d for d in range(1, POS_EDGE_FILL + 1) if d % 4 == j % 4]
+        assert extras <= len(cls) - 120 * (j // 4)
+        for d in cls[120 * (j // 4):120 * (j // 4) + extras]:
+            p = self.fill_pos.get(d, 0) + 1
+            self.fill_pos[d] = p
+            self._put(name, d, [p])
+        self.term_info[name] = dict(dense=extras >= 480, wide=wide, extras=extras)
+
+    def group(self, name, T, docs, flavours, share=None):
+        """docs: [lists in query order]; flavours: {tag: (extras per term, position offset)}; share: {tag: family} — the terms of that flavour are the
+        family's, which several groups hold (a conjunction of more than 64 documents).  Returns {tag: [terms]} and the docids."""
+        n = len(docs)
+        assert n <= 64
+        if (self.next_doc - 1) % 256 + n > 256:
+            self.next_doc = ((self.next_doc - 1) // 256 + 1) * 256 + 1
+        dids = list(range(self.next_doc, self.next_doc + n))
+        self.next_doc += n
+        assert self.next_doc - 1 <= POS_EDGE_LASTDOCID
+        terms = {}
+        for tag, (extras, off) in flavours.items():
+            names = ["%s%s%s" % ((share or {}).get(tag, name), tag, "abcdefgh"[j]) for j in range(T)]
+            wide = [any(p + off >= 65536 for lists in docs for p in lists[j]) for j in range(T)]
+            for j, t in enumerate(names):
+                if t not in self.term_info:
+                    self.term(t, j, extras[j], wide[j])
+                assert self.term_info[t]["wide"] == wide[j]
+                for d, lists in zip(dids, docs):
+                    self._put(t, d, [p + off for p in lists[j]])
+            terms[tag] = names
+        self.groups[name] = dict(dids=dids, docs=docs, terms=terms, offs={tag: off for tag, (_, off) in flavours.items()})
+        return terms, dids
+
+    def case(self, name, op, terms, window, group, perm=None, aimed=()):
+        """A table entry.  perm: the query's terms are the group's in this order (the lists follow).  aimed: [(index of the group's document,
+        intended verdict)] — the documents crafted for this very case."""
+        self.cases.append(dict(name=name, edge=name.split("_")[0], op=op, terms=list(terms), window=window, group=group, perm=list(perm) if perm else None,
+                               first=0, maxitems=POS_EDGE_MAXITEMS))
+        for i, v in aimed:
+            self.intent[(name, self.groups[group]["dids"][i])] = v
+
+
+D2, F2, R2 = (484, 500), (0, 500), (0, 6)                      # two terms: both with containers | a rare leader | both rare
+_FL2 = {"d": (D2, 0), "f": (F2, POS_EDGE_FLAVOUR_STEP), "r": (R2, 2 * POS_EDGE_FLAVOUR_STEP)}
+_OPS3 = (("ex", "PHRASE", 0), ("win", "PHRASE", 3), ("near", "NEAR", 2))        # tag, op, window - number of terms (0: exact)
+_X8 = (10, 2, 14, 6, 0, 12, 4, 8)                             # filler postings of a rare term by its place in the query: plan order != query order
+
+
+def _win(T, extra):
+    return T + extra if extra else 0
+
+
+_pos_edge_cache = None
+
+
+def _positional_edges():
+    global _pos_edge_cache
+    if _pos_edge_cache is not None:
+        return _pos_edge_cache
+    B = _PosEdgeBuilder()
+    rng = B.rng
+
+    def two(edge, gname, tag, op, window, docs, aimed, flavours=_FL2, share=None):
+        """A two-term group in its flavours, asked in both query orders where the order is free (NEAR)."""
+        terms, _ = B.group(gname, 2, docs, flavours, share)
+        for fl, names in terms.items():
+            if fl in (share or {}):
+                continue
+            B.case("%s_%s%s_%s" % (edge, gname, fl, tag), op, names, window, gname, aimed=aimed)
+            if op == "NEAR":
+                B.case("%s_%s%s_%s_rev" % (edge, gname, fl, tag), op, names[::-1], window, gname, perm=[1, 0], aimed=aimed)
+
+    # -- len: the length of a term's list, 2-byte lists; the deciding entry is the list's last; the long list under plan term 0 (a) and under the last (b)
+    for tag, op, extra in _OPS3:
+        docs, aimed = [], []
+        for n in LEN16:
+            for p_long in (0, 1):
+                for match in (True, False):
+                    docs.append(_craft_lists(op, _win(2, extra), 2, p_long, n, n - 1, match))
+                    aimed.append((len(docs) - 1, match))
+        two("len", "l" + tag, tag, op, _win(2, extra), docs, aimed)
+    # -- len4: 4-byte lists (every position past 65 535).  The exact group's terms sort last and its last document is the 254-entry list whose
+    #    match is its last entry: the last list of the positions section
+    for tag, op, extra in _OPS3:
+        docs, aimed = [], []
+        for n in LEN32:
+            for p_long in (0, 1):
+                for match in (False, True):
+                    docs.append([[p + 66000 for p in pp] for pp in _craft_lists(op, _win(2, extra), 2, p_long, n, n - 1, match)])
+                    aimed.append((len(docs) - 1, match))
+        gname = "zz4" if tag == "ex" else "q" + tag
+        two("len4", gname, tag, op, _win(2, extra), docs, aimed, flavours={"d": (D2, 0), "r": (R2, 40000)})
+    # -- idx: where in the long list the deciding entry sits: lists of 16 (fast), 64 (wide), 254 (serial)
+    for gname, op, extra, p_long in (("ia", "PHRASE", 0, 0), ("ib", "PHRASE", 0, 1), ("in", "NEAR", 2, 0), ("iw", "PHRASE", 1, 1)):
+        docs, aimed = [], []
+        for n in (16, 64, 254):
+            for idx in sorted({i for i in DECISIVE if i < n} | {n - 1}):
+                for match in (True, False):
+                    docs.append(_craft_lists(op, _win(2, extra), 2, p_long, n, idx, match))
+                    aimed.append((len(docs) - 1, match))
+        fam = gname in ("ia", "ib")
+        two("idx", gname, {"PHRASE": "ex" if not extra else "win", "NEAR": "near"}[op], op, _win(2, extra), docs, aimed,
+            flavours=dict(_FL2, u=(D2, 3 * POS_EDGE_FLAVOUR_STEP)) if fam else _FL2, share={"u": "iu"} if fam else None)
+    # -- round: what a round of 64 survivors is made of.  f: at most 16 positions of a term, w: 17 .. 64, s: more; verdicts alternate
+    kinds = {"f": (1, 2, 3, 5, 8, 9, 12, 16), "w": (17, 20, 31, 32, 33, 48, 64), "s": (65, 100, 254)}
+    rounds = (("f64", "f" * 64), ("w16", "w" * 16), ("w17", "w" * 17), ("w33", "w" * 33), ("w64", "w" * 64), ("s1st", "s" + "f" * 63), ("slast", "f" * 63 + "s"),
+              ("mix", "fwsfwfsw" * 8))
+    for gname, comp in rounds:
+        docs, aimed = [], []
+        for i, k in enumerate(comp):
+            n = rng.choice(kinds[k])
+            docs.append(_craft_lists("PHRASE", 0, 2, i // 2 % 2, n, rng.randrange(n), i % 2 == 0))
+            aimed.append((i, i % 2 == 0))
+        fam = gname in ("w64", "mix")
+        two("round", "r" + gname, "ex", "PHRASE", 0, docs, aimed, flavours=dict({"d": (D2, 0), "f": (F2, POS_EDGE_FLAVOUR_STEP)}, **({"v": (R2, 2 * POS_EDGE_FLAVOUR_STEP)} if fam else {})),
+            share={"v": "ru"} if fam else None)
+    # -- several: conjunctions of more than 64 documents (two groups that share a flavour's terms): more than one round of survivors, and at a page
+    #    of ten a k-th weight that drops candidates before their positions are tested
+    for fam, fl, gs in (("iu", "u", ["ia", "ib"]), ("ru", "v", ["rw64", "rmix"])):
+        names = B.groups[gs[0]]["terms"][fl]
+        assert names == B.groups[gs[1]]["terms"][fl]
+        for tag, op, extra in _OPS3:
+            B.case("several_%s%s_%s" % (fam, fl, tag), op, names, _win(2, extra), gs)
+    # -- plan: the long list under plan term 0, the last, and (5 and 8 terms) plan terms 4 and 7; lists of 12 (fast), 20 (wide), 70 (serial)
+    for T, flavours in ((3, ("d", "f")), (4, ("d", "f")), (5, ("r",)), (8, ("r",))):
+        order = sorted(range(T), key=lambda j: _X8[j])                       # plan order: ascending termfreq
+        where = sorted({0, T - 1} | ({4} if T > 4 else set()))
+        docs, aimed_by = [], {}
+        for tag, op, extra in _OPS3:
+            for k in where:
+                for n in (12, 20, 70):
+                    for match in (True, False):
+                        docs.append(_craft_lists(op, _win(T, extra), T, order[k], n, n - 1, match))
+                        aimed_by.setdefault(tag, []).append((len(docs) - 1, match))
+        fl = {}
+        for f in flavours:
+            ex = [_X8[j] for j in range(T)]
+            if f == "d": ex = [480 + 2 * e for e in ex]
+            if f == "f": ex = [0 if e == min(ex) else 480 + 2 * e for e in ex]
+            fl[f] = (ex, POS_EDGE_FLAVOUR_STEP * len(fl))
+        terms, _ = B.group("p%d" % T, T, docs, fl)
+        for f, names in terms.items():
+            for tag, op, extra in _OPS3:
+                B.case("plan_p%d%s_%s" % (T, f, tag), op, names, _win(T, extra), "p%d" % T, aimed=aimed_by[tag])
+    # -- width: a phrase that ends at 65 535 (both lists 2-byte), one at 65 535 / 65 536 (a 2-byte and a 4-byte term, in both plan orders)
+    docs = [[[65534], [65535]], [[65533], [65535]], [[7, 65534], [9, 30, 65535]], [[7, 65533], [9, 30, 65535]]]
+    terms, _ = B.group("w16", 2, docs, {"d": (D2, 0)})
+    B.case("width_w16d_ex", "PHRASE", terms["d"], 0, "w16", aimed=[(0, True), (1, False), (2, True), (3, False)])
+    B.case("width_w16d_near", "NEAR", terms["d"][::-1], 2, "w16", perm=[1, 0], aimed=[(0, True), (1, False), (2, True), (3, False)])
+    terms, _ = B.group("w16r", 2, docs, {"r": (R2, 0)})
+    B.case("width_w16r_ex", "PHRASE", terms["r"], 0, "w16r", aimed=[(0, True), (1, False), (2, True), (3, False)])
+    docs = [[[65535], [65536]], [[65534], [65536]], [[3, 40, 65535], [5, 65536]], [[3, 40, 65534], [5, 65536]], [[100], [101]], [[100], [102]]]
+    aimed = [(i, i % 2 == 0) for i in range(6)]
+    for gname, fl in (("wma", {"d": (D2, 0)}), ("wmb", {"d": ((500, 484), 0)}), ("wmr", {"r": (R2, 0)}), ("wms", {"r": ((6, 0), 0)})):     # the 4-byte term last / first in the plan
+        terms, _ = B.group(gname, 2, docs, fl)
+        f = next(iter(fl))
+        B.case("width_%s%s_ex" % (gname, f), "PHRASE", terms[f], 0, gname, aimed=aimed)
+        B.case("width_%s%s_win" % (gname, f), "PHRASE", terms[f], 4, gname)
+        B.case("width_%s%s_near" % (gname, f), "NEAR", terms[f][::-1], 2, gname, perm=[1, 0], aimed=aimed)
+    # -- exact: a word below its phrase index, position 0, the rarest term the last word, eight words
+    docs = [[[0], [1], [2]], [[0], [1], [3]], [[5], [6, 9], [1, 7]], [[5], [6, 9], [1, 8]], [[4], [0, 5], [1, 6]], [[4], [0, 6], [1, 7]],
+            [[9], [1], [0]], [[3, 30], [1, 31], [0, 2, 32]], [[3, 30], [1, 31], [0, 2, 33]]]
+    aimed = [(0, True), (1, False), (2, True), (3, False), (4, True), (5, False), (6, False), (7, True), (8, False)]
+    terms, _ = B.group("ex3", 3, docs, {"d": ((500, 492, 484), 0), "f": ((500, 492, 0), POS_EDGE_FLAVOUR_STEP)})     # the rarest term is the last word
+    for f, names in terms.items():
+        B.case("exact_ex3%s" % f, "PHRASE", names, 0, "ex3", aimed=aimed)
+    docs, aimed = [], []
+    for p_long, n in ((0, 1), (3, 9), (7, 20), (2, 70)):
+        for match in (True, False):
+            docs.append(_craft_lists("PHRASE", 0, 8, p_long, n, n - 1, match))
+            aimed.append((len(docs) - 1, match))
+    docs += [[[j] for j in range(8)], [[j if j < 7 else 8] for j in range(8)]]                    # from position 0
+    aimed += [(len(docs) - 2, True), (len(docs) - 1, False)]
+    terms, _ = B.group("ex8", 8, docs, {"r": (_X8, 0)})
+    B.case("exact_ex8r", "PHRASE", terms["r"], 0, "ex8", aimed=aimed)
+    # -- window: b - base equal to the window and one more (with every window), a first base that fails and a later one that fits, the greedy
+    #    walk's restart from b - window, a later word's list running out
+    for T in (2, 3, 4):
+        for extra in (1, 3, 40):
+            w = T + extra
+            docs, aimed = [], []
+            for p_long, n in ((0, 1), (T - 1, 9), (0, 20), (T - 1, 70)):
+                for match in (True, False):
+                    docs.append(_craft_lists("PHRASE", w, T, p_long, n, n // 2, match))
+                    aimed.append((len(docs) - 1, match))
+            first = [[10 + j, 200 + j] for j in range(T)]
+            first[-1] = [10 + w, 200 + w - 1]                                  # base 10 fails by one, base 200 fits at equality
+            late = [[10 + j, 300 + j] for j in range(T)]
+            late[-1] = [10 + w + 1, 300 + w]                                                          # both bases fail, the second by one
+            out = [[10 + j, 400 + j] for j in range(T)]
+            out[-1] = [10 + w + 5]                                                                    # the last word's list runs out under the second base
+            skip = [[10 + j] for j in range(T)]
+            skip[0] = [10, 12 + w, 500]; skip[-1] = [11 + 2 * w]                                      # the restart at b - window passes over a base
+            docs += [first, late, out, skip]
+            aimed += [(len(docs) - 4, True), (len(docs) - 3, False), (len(docs) - 2, False)]
+            fl = {"d": ([480 + 2 * _X8[j] for j in range(T)], 0), "f": ([0 if _X8[j] == min(_X8[:T]) else 480 + 2 * _X8[j] for j in range(T)], POS_EDGE_FLAVOUR_STEP)}
+            terms, _ = B.group("v%d%d" % (T, extra), T, docs, fl)
+            for f, names in terms.items():
+                B.case("window_v%d_%d%s" % (T, extra, f), "PHRASE", names, w, "v%d%d" % (T, extra), aimed=aimed)
+    # -- near: span == window - 1 and == window for window n, n + 2, 40 and 70 000; every term order; all heads below the window; the
+    #    smallest head's list running out; 2 .. 8 terms
+    import itertools
+    for T in (2, 3, 4, 6, 8):
+        docs, aimed_by = [], {}
+        for w in (T, T + 2, 40, 70000):
+            for p_long, n in ((0, 1), (T - 1, 9), (T // 2, 20), (0, 70)):
+                for match in (True, False):
+                    docs.append(_craft_lists("NEAR", w, T, p_long, n, n - 1, match, stride=64 if w < 60 else 80000))
+                    aimed_by.setdefault(w, []).append((len(docs) - 1, match))
+        low = [[1 + j] for j in range(T)]                                                             # every head below every window
+        runs_out = [[5 + j, 5000 + 3 * j] for j in range(T)]
+        runs_out[0] = [5]; runs_out[-1] = [4000, 5000 + 3 * T]                                      # term 0 holds the smallest head and has nothing further
+        docs += [low, runs_out]
+        for w in (T, T + 2, 40, 70000):
+            aimed_by[w] += [(len(docs) - 2, True), (len(docs) - 1, w == 70000)]
+        # (the lists of the 70 000 window reach past 65 535: these terms have 4-byte lists throughout — the 2-byte NEAR lists are len / idx / plan's)
+        terms, _ = B.group("n%d" % T, T, docs, {"r": (_X8[:T], 0)})
+        perms = list(itertools.permutations(range(T))) if T <= 3 else [tuple(range(T)), tuple(reversed(range(T))), tuple(rng.sample(range(T), T))]
+        for f, names in terms.items():
+            for w in (T, T + 2, 40, 70000):
+                for pi, perm in enumerate(perms if w in (T, T + 2) else perms[:1]):
+                    B.case("near_n%d%s_w%d_o%d" % (T, f, w, pi), "NEAR", [names[j] for j in perm], w, "n%d" % T, perm=perm, aimed=aimed_by[w])
+    assert len({c["name"] for c in B.cases}) == len(B.cases)
+    live = set(range(1, POS_EDGE_LASTDOCID + 1))
+    for d in live:
+        if d not in B.doclen:                      # a document no group reached: one filler posting of its own, so that every docid is a document
+            B._put("fill", d, [1])
+    _pos_edge_cache = B
+    return B
+
+
+def positional_edge_postings():
+    """(postings {term: [(did, wdf, [positions])]}, doclen {did: Σ wdf}) of the positional filter's edge corpus: 3 839 documents (15 stripes), built for
+    stripe_bits = 8.  Every posting has exactly wdf positions; the positions inside a document are pairwise distinct."""
+    B = _positional_edges()
+    return B.post, B.doclen
+
+
+def positional_edge_cases():
+    """[dict(name, edge, op, terms, window, first, maxitems, group, perm)]: the table; the name's first word is the edge cell."""
+    return [dict(c) for c in _positional_edges().cases]
+
+
+def positional_edge_lists(case):
+    """{docid: the lists in QUERY order} of the case's conjunction (its group), and {docid: intended verdict} for the documents crafted for it."""
+    B = _positional_edges()
+    lists = {}
+    for gname in case["group"] if isinstance(case["group"], list) else [case["group"]]:
+        g = B.groups[gname]
+        fl = next(f for f, names in g["terms"].items() if set(names) == set(case["terms"]))
+        off, perm = g["offs"][fl], case["perm"] or list(range(len(case["terms"])))
+        lists.update({d: [[p + off for p in docs[j]] for j in perm] for d, docs in zip(g["dids"], g["docs"])})
+    return lists, {d: v for (n, d), v in B.intent.items() if n == case["name"]}
+
+
+def positional_edge_term_info():
+    """{term: dict(dense, wide, extras)}: which terms are meant to have containers, which 4-byte lists."""
+    return dict(_positional_edges().term_info)

@@ -25,6 +25,12 @@ def shards_for(fx):
             assert fx["tree_edges"]["lastdocid"] == H.TREE_EDGE_LASTDOCID
             _cache[key] = [H.ManualCorpus(*H.tree_edge_postings())]
         return _cache[key]
+    if "positional_edges" in fx:           # the crafted corpus of the positional filter's edges (helpers.positional_edge_postings)
+        key = ("positional_edges", fx["positional_edges"]["lastdocid"], fx["positional_edges"]["seed"])
+        if key not in _cache:
+            assert key[1:] == (H.POS_EDGE_LASTDOCID, H.POS_EDGE_SEED)
+            _cache[key] = [H.ManualCorpus(*H.positional_edge_postings())]
+        return _cache[key]
     c = fx["corpus"]
     key = (c["seed"], c["n_docs"], c["vocab"], fx["n_shards"])
     if key not in _cache:
@@ -50,6 +56,8 @@ def test_oracle_matches_golden(path):
     assert fx["results"]
     for r in fx["results"]:
         q = r["query"]
+        if r.get("reference_crashed"):         # recorded without an answer (positional_edges: at most three, named in DESIGN.md)
+            continue
         if q["op"] == "RPN":
             rows, hdr, total_subqs = H.oracle_search_tree(shards[0], H.tree_from_json(q["tree"]), q["first"], q["maxitems"])
             page = rows[q["first"]:]
@@ -79,6 +87,14 @@ def test_oracle_matches_golden(path):
                                         reference_select_bug="coloc" in fx)
             got = [(d, w) for d, w, _ in hits[q["first"]:]]
             assert hdr.max_possible == float.fromhex(r["max_possible"])
+            if "positional_edges" in fx:       # whole matches: the count is the page; the percentages: every term of a positional match matches
+                assert hdr.matches == len(hits) <= H.POS_EDGE_MAX_CONJ, q
+                assert not hits or hdr.max_attained == float.fromhex(r["max_attained"]), q
+                pct = H.tree_percentages(hits, hdr, len(q["terms"])) if hits else []
+                if "hits" not in r:            # a long page: its length and digest
+                    assert (len(hits), hits_digest(hits, pct)) == (r["n_hits"], r["hits_sha256"]), q
+                    continue
+                assert pct == [p for _, _, p in r["hits"]], q
         else:
             got = [(d, w) for d, w, _ in H.oracle_search_sharded(shards, q["op"], q["terms"], q["first"], q["maxitems"])]
         assert got == expected(r), q
